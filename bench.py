@@ -16,6 +16,9 @@ regenerates its own subframes): payloads = mi355_enb_synth_payloads(i) -> the pr
 (40 dB) -> IFFT + CP; sf_idx = i % 10.
 
     python bench.py [--gpus N --steps K --warmup W]     # N > 1: re-launches itself under torch.distributed.run
+    python bench.py --full                              # + roofline probes, CPU baselines, configs[0], drop-in
+                                                        #   latency, waterfall, payload comparison (after the timing)
+    python bench.py --dump-outputs DIR                  # the last timed step's outputs as DIR/<name>.npy
     python bench.py --gpus 8 --total-subframes 1048576  # configs[4]: 1M subframes sharded contiguously by rank
     python bench.py --workload tdec                     # configs[1]: batched turbo decode only
     python bench.py --workload ue_dl                    # + PCFICH / PDCCH blind search -> DCI -> grant
@@ -105,7 +108,23 @@ def parse(argv=None):
     ap.add_argument("--fanout", action="store_true",
                     help="batch fan-out: rank 0 holds every rank's I/Q and scatters the shards over RCCL each step "
                          "(pdsch / ue_dl / plumbing workloads); payload SHA-1s and CRC bitmaps gathered back")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every secondary leg: per-stage and MAP-kernel roofline "
+                         "probes, CPU baselines, configs[0], the drop-in latency loop, the waterfall with its AVX2 "
+                         "parity and the payload comparison (--no-cpu / --no-roofline / --no-waterfall take legs out "
+                         "again).  Without it a run sets up, warms up, times --steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned to its caller as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB in all: a fixed seeded sample of the "
+                         "larger arrays); rank 0 only; workloads pdsch, ue_dl, siso_qpsk and tdec")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.workload in ("enb", "plumbing") or args.fanout or args.total_subframes):
+        ap.error("--dump-outputs: only the pdsch, ue_dl, siso_qpsk and tdec workloads (without --fanout / "
+                 "--total-subframes) write their outputs")
+    if not args.full:
+        args.no_cpu = args.no_roofline = args.no_waterfall = True
     if args.subframes is None:
         args.subframes = 8192 if args.workload == "siso_qpsk" else 2048
     if args.workers is None:
@@ -460,7 +479,7 @@ def Tm4Rx(cell, B, device, ctrl=False):
     return DlReceiver(cell, 2, B, NB, device, ctrl=ctrl, max_cb=16, ce_rows=1)
 
 
-CALLER_SO = os.path.join(ROOT, "tests", "dropin", "libdropin_caller.so")
+CALLER_SO = os.path.join(ROOT, "oracle", "_ref", "libdropin_caller.so")
 
 
 class CallerCfg(C.Structure):  # caller_cfg_t of tests/dropin/caller.c
@@ -834,6 +853,54 @@ def call_stats(calls):
     return {"calls": int(a.size), "p50_ms": round(float(a[a.size // 2]), 3), "max_ms": round(float(a[-1]), 3)}
 
 
+DUMP_LIMIT = 64 << 20  # bytes --dump-outputs may write in all
+DUMP_SAMPLE_SEED = 20240  # the sampled rows are the same in every run
+
+
+def dump_sample(n: int, k: int) -> np.ndarray:
+    """min(n, k) of the rows 0..n-1, ascending: a fixed seeded choice, so two builds dump the same rows"""
+    if n <= k:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=k, replace=False))
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array as path/<name>.npy, float32 (float64 where given as such)"""
+    os.makedirs(path, exist_ok=True)
+    out = {k: np.ascontiguousarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32)
+           for k, v in arrays.items()}
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs would write {total} bytes"
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
+def receiver_outputs(rx, n, nbytes, rows_pay=256, rows_grid=16) -> dict:
+    """What the caller of rx's last step (n subframes) received: per TB the CRC flag, return code and mean
+    half-iterations (mi355_pdsch_res_t), per subframe the estimator's measurements (mi355_chest_res_t: noise, SNR,
+    RSRP, RSRQ, CFO ...), with the control channels the CFI / DCI count, and of a fixed sample of the subframes the
+    decoded TB bytes and the demodulated resource grid (re, im)."""
+    from srsran_amd import lib
+    res = np.ctypeslib.as_array(rx.res)[: 2 * n]
+    words = np.frombuffer(rx.chest, np.uint32).reshape(rx.B, -1)[:n]
+    out = {"tb_crc": res["crc"].reshape(n, 2), "tb_ret": res["ret"].reshape(n, 2),
+           "tb_avg_half_iterations": res["avg_iterations_block"].reshape(n, 2),
+           "chest_nof_re": words[:, 0], "chest_measurements": words[:, 1:].view(np.float32)}
+    if rx.ctrl:
+        cr = np.ctypeslib.as_array(rx.ctrl_res)[:n]
+        out["ctrl"] = np.stack([cr[f].astype(np.float32) for f in ("cfi", "cfi_corr", "nof_dci", "nof_cce")], axis=1)
+    sp = dump_sample(n, rows_pay)
+    out["payload_subframes"] = sp
+    out["payload_bytes"] = rx.received(n)[sp, :, :nbytes]
+    sg = dump_sample(n, rows_grid)
+    grid = np.zeros((sg.size, rx.nof_rx, rx.G, 2), np.float32)
+    for i, k in enumerate(sg):
+        lib().mi355_memcpy_d2h(grid[i].ctypes.data, rx.grid_ptr(int(k), 0), grid[i].nbytes)
+    out["grid_subframes"] = sg
+    out["grid"] = grid
+    return out
+
+
 def run_pdsch(args, world, rank, local, pg):
     if args.total_subframes:
         return run_pdsch_total(args, world, rank, local, pg)
@@ -879,11 +946,14 @@ def run_pdsch(args, world, rank, local, pg):
         barrier(pg, local)
         dt_total += time.perf_counter() - t0
         batches += reps * len(bound)
-        if bound:  # payload check of the batch every worker decoded last
+        if bound:
             wk = rxs[: min(W, reps)]
-            for r, wb in zip(wk, wbound):
-                ok_sample += r.payload_ok(src, wb[-1])
-                sample_tbs += 2 * wb[-1][3]
+            if args.dump_outputs and rank == 0:  # the last timed step ran on worker (reps - 1) mod W
+                dump_outputs(args.dump_outputs, receiver_outputs(rxs[(reps - 1) % W], bound[-1][3], NB))
+            if args.full:  # payload check of the batch every worker decoded last
+                for r, wb in zip(wk, wbound):
+                    ok_sample += r.payload_ok(src, wb[-1])
+                    sample_tbs += 2 * wb[-1][3]
             its_all.append(rx.avg_its(bound[-1][3]))
             b = rx.crc_bits(bound[-1][3])
             for r, wb in zip(wk[1:], wbound[1:]):
@@ -913,7 +983,7 @@ def run_pdsch(args, world, rank, local, pg):
                    "parallelism": f"dp{world}"},
         "crc_ok_tbs": f"{ok_tbs}/{2 * nsf}",
         "crc_bitmap": bitmap_summary(gathered, nsf) if rank == 0 else None,
-        "payload_checked_tbs": f"{ok_sample_all}/{sample_all}",
+        "payload_checked_tbs": f"{ok_sample_all}/{sample_all}" if args.full else None,
         "avg_half_iterations": round(its, 3),
     })
     if args.no_roofline:
@@ -1233,7 +1303,12 @@ def run_siso(args, world, rank, local, pg):
     for r in rxs[1: min(W, args.steps)]:
         bits &= r.crc_bits(B).reshape(B, 2)[:, 0]  # a TB counts only if every worker decoded it
     gathered = gather_bitmap(pg, local, bits)
-    ok_pay = int(sum_over_ranks(pg, local, min(r.payload_ok(src, wb[0]) for r, wb in zip(rxs[: max(1, min(W, args.steps))], wbound))))
+    if args.dump_outputs and rank == 0:  # the last timed step ran on worker (steps - 1) mod W
+        dump_outputs(args.dump_outputs, receiver_outputs(rxs[(args.steps - 1) % W], B, nb))
+    ok_pay = None
+    if args.full:
+        ok_pay = int(sum_over_ranks(pg, local, min(r.payload_ok(src, wb[0])
+                                                   for r, wb in zip(rxs[: max(1, min(W, args.steps))], wbound))))
     its = rx.avg_its(B) * 2  # the disabled second TB reads 0
     ok_tbs = int(gathered.sum()) if rank == 0 else 0
     mbps = whole_job_rate(world, B * SISO_TBS, args.steps, dt) / 1e6 * (ok_tbs / (B * world))
@@ -1252,7 +1327,8 @@ def run_siso(args, world, rank, local, pg):
            "code_blocks_per_s": round(world * SISO_C * B * args.steps / dt, 1),
            "subframes_per_s": round(world * B * args.steps / dt, 1),
            "crc_ok_tbs": f"{ok_tbs}/{B * world}", "crc_bitmap": bitmap_summary(gathered, B * world) if rank == 0 else None,
-           "payload_checked_tbs": f"{ok_pay}/{B * world}", "avg_half_iterations": round(its, 3)}
+           "payload_checked_tbs": f"{ok_pay}/{B * world}" if args.full else None,
+           "avg_half_iterations": round(its, 3)}
     if not args.no_roofline:
         roof, valu, fixed8, (ptr, stride, _d_out) = map_probe(rx, SISO_C * B, local, K=SISO_K, mode="siso")
         res["roofline"], res["roofline_valu"], res["decoder_bound_fixed8"] = roof, valu, fixed8
@@ -1471,8 +1547,6 @@ def run_tdec(args, world, rank, local, pg):
     for _ in range(args.warmup):
         step()
     lib().mi355_device_sync()
-    got = np.zeros((ncb, K // 8), np.uint8)
-    d_out.download(got)
     barrier(pg, local)
     lib().mi355_device_sync()
     t0 = time.perf_counter()
@@ -1481,28 +1555,37 @@ def run_tdec(args, world, rank, local, pg):
     lib().mi355_device_sync()
     barrier(pg, local)
     dt = max_over_ranks(pg, local, time.perf_counter() - t0)
-    dec.set_profiling(True)
-    for _ in range(2):
-        step()
-    kms, kl = dec.kernel_stats()
-    # the kernel's bandwidth-only clone (mi355_tdec_set_diag(20): same grid, loads, checkpoint stores, extrinsic
-    # scatter, one xor per trellis step): the time this schedule's memory traffic alone takes on this box
-    old = lib().mi355_tdec_set_diag(20)
-    d_junk = DeviceBuffer(ncb * (K // 8), local)  # the clone's decisions are meaningless: kept out of d_out
-    for _ in range(2):
-        dec.run_dev(d_in.ptr, stride, ncb, K, nh, d_junk.ptr)
-    cms, cl = dec.kernel_stats()
-    lib().mi355_tdec_set_diag(old)
-    d_junk.free()
-    dec.set_profiling(False)
-    roof, valu = tdec_roofline(kms, kl, ncb, K, "tdec")
-    if cl:
-        clone = cms / cl
-        roof["schedule_clone_ms"] = round(clone, 4)
-        roof["schedule_frac"] = round(clone / roof["avg_launch_ms"], 4)
-        roof["schedule_note"] = ("bandwidth-only clone of tdec_win_halfit (MI355_TDEC_DIAG 20) over the same "
-                                 f"{ncb:,}-CB launches: schedule_frac = clone time / real time (1.0 = the trellis math "
-                                 "is fully hidden under this schedule's memory traffic)")
+    # every step decodes the same input, so the decisions read here are the last timed step's
+    got = np.zeros((ncb, K // 8), np.uint8)
+    if args.dump_outputs or not args.no_cpu:
+        d_out.download(got)
+    if args.dump_outputs and rank == 0:
+        rows = dump_sample(ncb, max(1, (DUMP_LIMIT // 2) // (4 * K)))
+        dump_outputs(args.dump_outputs, {"code_blocks": rows, "decisions": np.unpackbits(got[rows], axis=1)})
+    roof = valu = None
+    if not args.no_roofline:
+        dec.set_profiling(True)
+        for _ in range(2):
+            step()
+        kms, kl = dec.kernel_stats()
+        # the kernel's bandwidth-only clone (mi355_tdec_set_diag(20): same grid, loads, checkpoint stores, extrinsic
+        # scatter, one xor per trellis step): the time this schedule's memory traffic alone takes on this box
+        old = lib().mi355_tdec_set_diag(20)
+        d_junk = DeviceBuffer(ncb * (K // 8), local)  # the clone's decisions are meaningless: kept out of d_out
+        for _ in range(2):
+            dec.run_dev(d_in.ptr, stride, ncb, K, nh, d_junk.ptr)
+        cms, cl = dec.kernel_stats()
+        lib().mi355_tdec_set_diag(old)
+        d_junk.free()
+        dec.set_profiling(False)
+        roof, valu = tdec_roofline(kms, kl, ncb, K, "tdec")
+        if cl:
+            clone = cms / cl
+            roof["schedule_clone_ms"] = round(clone, 4)
+            roof["schedule_frac"] = round(clone / roof["avg_launch_ms"], 4)
+            roof["schedule_note"] = ("bandwidth-only clone of tdec_win_halfit (MI355_TDEC_DIAG 20) over the same "
+                                     f"{ncb:,}-CB launches: schedule_frac = clone time / real time (1.0 = the trellis "
+                                     "math is fully hidden under this schedule's memory traffic)")
     cb_s = world * ncb * args.steps / dt
     res = {
         "metric": METRIC, "value": round(cb_s * K / 1e6, 1), "unit": "Mbps", "n_gpus": world,
@@ -1599,8 +1682,7 @@ def run_enb(args, world, rank, local, pg):
     lib().mi355_device_sync()
     barrier(pg, local)
     dt = max_over_ranks(pg, local, time.perf_counter() - t0)
-    ok = decode_check(cell, B, d_iq, payloads, local)
-    ok_all = int(sum_over_ranks(pg, local, ok))
+    ok_all = int(sum_over_ranks(pg, local, decode_check(cell, B, d_iq, payloads, local))) if args.full else None
     mbps = whole_job_rate(world, B * 2 * TBS, args.steps, dt) / 1e6
     # algorithmic HBM bytes per subframe of the chain: payload in, codeword bits out + in, PDSCH and
     # CRS REs out, channel grids in + out, IFFT grids in + I/Q out
@@ -1616,7 +1698,7 @@ def run_enb(args, world, rank, local, pg):
                                "QAM256 subframes/GPU/step (2 x TBS 97896, 32 CBs of K=6144 each), payloads in HBM",
                    "subframes_per_gpu": B, "parallelism": f"dp{world}"},
         "subframes_per_s": round(world * B * args.steps / dt, 1),
-        "decoded_back_ok_tbs": f"{ok_all}/{2 * B * world}",
+        "decoded_back_ok_tbs": f"{ok_all}/{2 * B * world}" if args.full else None,
         "roofline": {"bound": "hbm", "achieved": round(ach, 1), "peak": 8000.0, "unit": "GB/s",
                      "frac": round(ach / 8000.0, 4), "traffic": None, "kernel": "whole generator chain",
                      "algorithmic_bytes_per_subframe": per_sf},

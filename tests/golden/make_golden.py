@@ -46,6 +46,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
 import oracle  # noqa: E402
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+from golden_io import save_split  # noqa: E402
 
 OUT = os.path.dirname(os.path.abspath(__file__))
 REF_TEST_H = "/root/reference/lib/src/phy/fec/test/turbodecoder_test.h"
@@ -171,7 +173,7 @@ def gen_tdec8(rng):
         data[f"sb{k}_cinit"], data[f"sb{k}_in"], data[f"sb{k}_out"] = np.uint32(c_init), llr, out
         k += 1
     data["sb_n"] = np.int32(k)
-    np.savez_compressed(os.path.join(OUT, "tdec8.npz"), **data)
+    save_split(OUT, "tdec8.npz", data)  # over 1 MiB as one file: stored in parts, golden_io.load reads them
     print("tdec8.npz:", len(cases), "decoder cases,", len(rm), "rate-dematching cases")
 
 
@@ -504,7 +506,7 @@ def gen_pdcch(rng):
         data[f"sf{k}_msg"] = msgs[0]["bits"] if msgs else np.zeros(0, np.uint8)
         k += 1
     data["sf_n"] = np.int32(k)
-    np.savez_compressed(os.path.join(OUT, "pdcch.npz"), **data)
+    save_split(OUT, "pdcch.npz", data)  # over 1 MiB as one file: stored in parts, golden_io.load reads them
     print("pdcch.npz:", len(cells), "REG maps,", len(locs), "search spaces,", data["vit_n"], "Viterbi,",
           data["enc_n"], "DCI encode/decode,", k, "control regions")
 

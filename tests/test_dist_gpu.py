@@ -27,8 +27,8 @@ def _run(args, timeout=280):
 @pytest.mark.gpu
 @pytest.mark.timeout(300)
 def test_two_ranks_weak_scaling_on_one_gpu():
-    res = _run(["--gpus", "2", "--subframes", "256", "--steps", "2", "--warmup", "1", "--workers", "1", "--no-cpu",
-                "--no-roofline", "--no-waterfall"])
+    res = _run(["--gpus", "2", "--subframes", "256", "--steps", "2", "--warmup", "1", "--workers", "1", "--full",
+                "--no-cpu", "--no-roofline", "--no-waterfall"])
     assert res["n_gpus"] == 2 and res["scaling"] == "weak"
     assert res["crc_ok_tbs"] == "1024/1024"
     assert res["crc_bitmap"]["length_bits"] == 1024 and res["crc_bitmap"]["ok_tbs"] == 1024

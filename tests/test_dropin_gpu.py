@@ -1,5 +1,5 @@
 """The srslte_* drop-in on the GPU, exercised from a caller compiled against the REFERENCE headers
-(tests/dropin/caller.c -> libdropin_caller.so -> libsrslte_mi355.so -> libsrsran_amd.so).
+(tests/dropin/caller.c -> oracle/_ref/libdropin_caller.so -> libsrslte_mi355.so -> libsrsran_amd.so).
 
 * srslte_tdec_init_manual / run_all / get_nof_iterations / free (turbodecoder_test.c's calls) on the reference's
   golden code blocks: decisions bit-exact with the reference decoder's, AUTO and GENERIC.
@@ -25,7 +25,7 @@ from oracle import ue_dl_chain as uc
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CALLER = os.path.join(ROOT, "tests", "dropin", "libdropin_caller.so")
+CALLER = os.path.join(ROOT, "oracle", "_ref", "libdropin_caller.so")
 
 
 class CallerCfg(C.Structure):

@@ -83,7 +83,7 @@ def test_library_loads_without_a_gpu():
 
 
 def test_reference_header_caller_links():
-    caller = os.path.join(ROOT, "tests", "dropin", "libdropin_caller.so")
+    caller = os.path.join(ROOT, "oracle", "_ref", "libdropin_caller.so")
     if not os.path.exists(caller):
         pytest.skip("caller not built (needs the reference headers: make -C tests/dropin)")
     out = subprocess.run(["ldd", caller], check=True, capture_output=True, text=True).stdout

@@ -9,8 +9,8 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for lib in "$@"; do
   n=$(basename $lib .so)
-  MI355_LIB=$lib timeout -k 10 300 python3 bench.py --no-cpu --no-waterfall --steps 3 --warmup 1 > $OUT/e_$n.json 2> $OUT/e_$n.err
-  MI355_LIB=$lib timeout -k 10 300 python3 bench.py --workload tdec --no-cpu --steps 3 --warmup 1 > $OUT/t_$n.json 2> $OUT/t_$n.err
+  MI355_LIB=$lib timeout -k 10 300 python3 bench.py --full --no-cpu --no-waterfall --steps 3 --warmup 1 > $OUT/e_$n.json 2> $OUT/e_$n.err
+  MI355_LIB=$lib timeout -k 10 300 python3 bench.py --workload tdec --full --no-cpu --steps 3 --warmup 1 > $OUT/t_$n.json 2> $OUT/t_$n.err
   python3 -c "import json,sys; e=json.load(open(sys.argv[1]))['roofline']; t=json.load(open(sys.argv[2]))['roofline']; print(sys.argv[3], 'e2e:', e['avg_launch_ms'], e.get('schedule_clone_ms'), '| tdec:', t['avg_launch_ms'], t.get('schedule_clone_ms'))" $OUT/e_$n.json $OUT/t_$n.json $n
 done
 echo rc=0

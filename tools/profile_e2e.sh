@@ -7,7 +7,7 @@ TAG=${1:-cur}
 OUT=gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
-E="python3 bench.py --steps 2 --warmup 1 --no-cpu --no-roofline"
+E="python3 bench.py --steps 2 --warmup 1 --full --no-cpu --no-roofline"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o trace -- $E > $OUT/trace.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o fetch -- $E > $OUT/fetch.log 2>&1
 timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/write -o write -- $E > $OUT/write.log 2>&1

@@ -8,7 +8,7 @@ TAG=${1:-stall}
 OUT=gpurun_out/stall_$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
-B="python3 bench.py --workload tdec --steps 2 --warmup 1 --no-cpu"
+B="python3 bench.py --workload tdec --steps 2 --warmup 1 --full --no-cpu"
 timeout -k 10 60 rocprofv3 -L > $OUT/avail.txt 2>&1 || true
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_VMEM SQ_INSTS_VMEM_RD --output-format csv -d $OUT/sq -o sq -- $B > $OUT/sq.log 2>&1
 timeout -s KILL 120 rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum TCC_EA0_RDREQ_sum TCC_EA0_WRREQ_sum --output-format csv -d $OUT/tcc -o tcc -- $B > $OUT/tcc.log 2>&1
