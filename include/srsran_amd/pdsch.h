@@ -152,12 +152,21 @@ uint32_t mi355_pdsch_re_map(const mi355_cell_t* cell, const mi355_pdsch_grant_t*
 int mi355_pdsch_debug_stage(mi355_pdsch_t* q, uint32_t job, uint32_t cw, const float** d, const float** csi,
                             const int16_t** e);
 
+/* For tests of the receiver's two device caches: the bounds on the RE extraction maps (default 8192 entries) and on
+ * the packed descrambling sequences (default 4096); 0 keeps the current value.  Both are checked once per call,
+ * before the batch is planned, so a batch may exceed them by its own distinct allocations / c_init values. */
+int mi355_pdsch_debug_set_cache_limits(mi355_pdsch_t* q, uint32_t max_maps, uint32_t max_scr);
+
+/* The extraction map job `job` of the last call was planned with: device pointer to n grid indices (uint16, the
+ * order of mi355_pdsch_re_map), valid until the next call. */
+int mi355_pdsch_debug_job_map(mi355_pdsch_t* q, uint32_t job, const uint16_t** d_map, uint32_t* n);
+
 /* srsUE's pdsch_8bit_decoder option (cc_worker.cc:98-101: pdsch.llr_is_8bit = pdsch.dl_sch.llr_is_8bit = true):
  * int8 LLRs (srslte_demod_soft_demodulate_b, srslte_scrambling_sb_offset, the float CSI loop of pdsch.c:661-668)
  * and the 8-bit DL-SCH decode (see mi355_dlsch_decode8_dev).  mi355_pdsch_debug_stage's e then points to int8. */
 int mi355_pdsch_set_llr_8bit(mi355_pdsch_t* q, int enable);
 
-/* The channel estimates of the following decode calls (mi355_pdsch_decode_batch / _launch) are identical in every
+/* The channel estimates of the following calls (mi355_pdsch_decode_batch / _launch / _frontend) are identical in every
  * OFDM symbol, as the AVERAGE estimator writes them (chest_dl.c's subframe average): the equaliser reads their first
  * row only, and port-0 / spatial-multiplexing jobs take the fused equaliser (pdsch_eq_llr / pdsch_eq_rm), whose results
  * are the two-kernel path's bit for bit.  Default 0 (estimates may vary per symbol). */

@@ -248,7 +248,11 @@ def rx_front(cfg: Cfg, y: np.ndarray, ce: np.ndarray, noise: float, predecoder=N
     nre = idx.size
     sc, scaling = rho_b_mask(cfg)
     row = 12 * cfg.nof_prb
-    ys = (y[:, idx] * sc[idx // row][None, :]).astype(np.complex64)
+    # srslte_vec_sc_prod_cfc scales the real and the imaginary part (a complex product with (s + 0j) would turn a
+    # -0.0 part into +0.0, which the equalised zeros of an all-zero RE then inherit)
+    ys = np.ascontiguousarray(y[:, idx], np.complex64)
+    ys = (ys.view(np.float32).reshape(ys.shape + (2,)) * sc[idx // row][None, :, None]).astype(np.float32)
+    ys = np.ascontiguousarray(ys).view(np.complex64).reshape(ys.shape[:2])
     hs = ce[:, :, idx]
     nz = noise if cfg.mmse else 0.0
     x, csi = (predecoder or predecode)(ys, hs, cfg.nof_layers, cfg.codebook(), cfg.scheme, scaling, nz)

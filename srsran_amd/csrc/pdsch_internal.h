@@ -18,7 +18,7 @@ struct PdschJobDev {
   uint32_t        g0;      // first grid index of the allocation
   float2*         d[2];    // equalised + layer-demapped symbols per codeword (q->d)
   float*          csi[2];  // CSI per codeword symbol (q->csi)
-  uint32_t*       cmax;    // [2][cmax_stride]: per-block maxima of csi[cw] (float bits, csi >= 0)
+  uint32_t*       cmax;    // [2][cmax_stride]: per-block maxima of csi[cw] (csi_key: unsigned order = float order)
   uint32_t        cmax_stride;
   uint32_t        nof_re, nof_rx, nof_ports, nof_layers, scheme, cb;
   uint32_t        row;       // 12 * nof_prb: grid index -> OFDM symbol l'

@@ -98,8 +98,16 @@ __device__ __forceinline__ void mmse_2x2_csi(cf y0, cf y1, cf h00, cf h01, cf h1
   mmse_2x2_apply(y0, y1, w00, w01, w10, w11, x0, x1);
 }
 
-// max in the unsigned order of the bit patterns (the order fold_max reduces in; IEEE order for csi >= 0)
-__device__ __forceinline__ float bmax(float a, float b) { return __uint_as_float(max(__float_as_uint(a), __float_as_uint(b))); }
+// csi maxima (csi_correction's srslte_vec_max_fi, pdsch.c:653: the float order -- a zero-forcing equaliser on an
+// ill-conditioned channel gives negative csi, whose bit patterns are the largest in the unsigned order): per thread
+// as floats, across threads and blocks as unsigned maxima of keys whose unsigned order is the float order
+__device__ __forceinline__ float bmax(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ uint32_t csi_key(float v)
+{
+  const uint32_t u = __float_as_uint(v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ uint32_t csi_key_bits(uint32_t k) { return (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k; }
 
 
 } // namespace
@@ -282,7 +290,7 @@ __global__ __launch_bounds__(256) void pdsch_equalize(const PdschJobDev* __restr
   const uint32_t     base = blockIdx.x * 256 * EQ_U + threadIdx.x;
   if (J.fused || blockIdx.x * 256 * EQ_U >= J.units) return;
   const float noise = J.noise_dev ? *gptr(J.noise_dev) : J.noise;
-  float       m0 = 0.f, m1 = 0.f; // per-thread csi contributions for the maxima
+  float       m0 = -INFINITY, m1 = -INFINITY; // per-thread csi contributions for the maxima
   if (J.scheme == 1) {
 #pragma unroll 1
     for (int k = 0; k < EQ_U; k++)
@@ -401,7 +409,7 @@ __global__ __launch_bounds__(256) void pdsch_equalize(const PdschJobDev* __restr
   // per-block csi maxima (csi_correction's srslte_vec_max_fi, pdsch.c:653) for the LLR kernel: wave reduction,
   // then one store per block and codeword (no atomics)
   __shared__ uint32_t red[2][4];
-  uint32_t            b0 = __float_as_uint(m0), b1 = __float_as_uint(m1);
+  uint32_t            b0 = csi_key(m0), b1 = csi_key(m1);
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) {
     b0 = max(b0, (uint32_t)__shfl_xor((int)b0, o, 64));
@@ -678,38 +686,44 @@ __device__ __forceinline__ int wrap8(int v) { return (int)(int8_t)(uint8_t)(v & 
 __device__ __forceinline__ int sat8i(int v) { return v < -128 ? -128 : (v > 127 ? 127 : v); }
 __device__ __forceinline__ int abs8(int v) { return v == -128 ? -128 : (v < 0 ? -v : v); } // _mm_abs_epi8
 
+// the conversions behind them: cvttps2dq / cvttss2si (truncating) and cvtps2dq (round to nearest even), whose result
+// for a value outside int32 is INT32_MIN (a plain (int) saturates here): -128 after the saturating packs, 0 after the
+// scalar tails' wrap (tests/golden/demod_extremes.npz)
+__device__ __forceinline__ int cvt8t(float v) { return x86_cvt_i32(truncf(v)); }
+__device__ __forceinline__ int cvt8r(float v) { return x86_cvt_i32(rintf(v)); }
+
 __device__ __forceinline__ void demod8(const PdschCwDev& C, float re, float im, bool body, int* o)
 {
   switch (C.qm) {
     case 1: { // demod_bpsk_lte_b: float sum times the double M_SQRT1_2
       const double v = (double)(-20.0f * (re + im)) * 0.70710678118654752440;
-      o[0]           = wrap8((int)v);
+      o[0]           = wrap8((v >= -2147483648.0 && v < 2147483648.0) ? (int32_t)v : INT32_MIN);
       break;
     }
     case 2: {
       const float a = re * C.k8[0], b = im * C.k8[0];
-      o[0]          = body ? sat8i((int)a) : wrap8((int)a);
-      o[1]          = body ? sat8i((int)b) : wrap8((int)b);
+      o[0]          = body ? sat8i(cvt8t(a)) : wrap8(cvt8t(a));
+      o[1]          = body ? sat8i(cvt8t(b)) : wrap8(cvt8t(b));
       break;
     }
     case 4:
       if (body) {
-        const int sr = sat8i((int)rintf(re * -30.0f)), si = sat8i((int)rintf(im * -30.0f));
+        const int sr = sat8i(cvt8r(re * -30.0f)), si = sat8i(cvt8r(im * -30.0f));
         o[0] = sr, o[1] = si, o[2] = wrap8(abs8(sr) - 18), o[3] = wrap8(abs8(si) - 18);
       } else {
-        const int yr = wrap8((int)(30.0f * re)), yi = wrap8((int)(30.0f * im));
+        const int yr = wrap8(cvt8t(30.0f * re)), yi = wrap8(cvt8t(30.0f * im));
         o[0] = wrap8(-yr), o[1] = wrap8(-yi);
-        o[2] = wrap8((int)((float)abs(yr) - C.k8[1]));
-        o[3] = wrap8((int)((float)abs(yi) - C.k8[1]));
+        o[2] = wrap8(cvt8t((float)abs(yr) - C.k8[1]));
+        o[3] = wrap8(cvt8t((float)abs(yi) - C.k8[1]));
       }
       break;
     case 6:
       if (body) {
-        const int sr = sat8i((int)rintf(re * -40.0f)), si = sat8i((int)rintf(im * -40.0f));
+        const int sr = sat8i(cvt8r(re * -40.0f)), si = sat8i(cvt8r(im * -40.0f));
         const int ar = wrap8(abs8(sr) - 24), ai = wrap8(abs8(si) - 24);
         o[0] = sr, o[1] = si, o[2] = ar, o[3] = ai, o[4] = wrap8(abs8(ar) - 12), o[5] = wrap8(abs8(ai) - 12);
       } else {
-        const int yr = wrap8((int)(40.0f * re)), yi = wrap8((int)(40.0f * im));
+        const int yr = wrap8(cvt8t(40.0f * re)), yi = wrap8(cvt8t(40.0f * im));
         o[0] = wrap8(-yr), o[1] = wrap8(-yi);
         o[2] = wrap8(wrap8(abs(yr)) - 24), o[3] = wrap8(wrap8(abs(yi)) - 24);
         o[4] = wrap8(wrap8(abs(o[2])) - 12), o[5] = wrap8(wrap8(abs(o[3])) - 12);
@@ -719,8 +733,8 @@ __device__ __forceinline__ void demod8(const PdschCwDev& C, float re, float im, 
       float r = -re, i = -im;
 #pragma unroll
       for (int k = 0; k < 4; k++) {
-        o[2 * k]     = wrap8((int)(50.0f * r));
-        o[2 * k + 1] = wrap8((int)(50.0f * i));
+        o[2 * k]     = wrap8(cvt8t(50.0f * r));
+        o[2 * k + 1] = wrap8(cvt8t(50.0f * i));
         if (k < 3) {
           r = fabsf(r) - C.k8[2 + k];
           i = fabsf(i) - C.k8[2 + k];
@@ -779,7 +793,7 @@ __global__ __launch_bounds__(256) void pdsch_cmax_reduce(const PdschCwDev* __res
   if (C.fused) return;
   uint32_t          b = 0;
   for (uint32_t k = 0; k < C.nparts; k++) b = max(b, gptr(C.cmax)[k]);
-  *gptr(C.cmax_final) = b;
+  *gptr(C.cmax_final) = csi_key_bits(b);
 }
 
 // ---------------------------------------------------------------------------- fused equaliser + LLR
@@ -861,8 +875,8 @@ __global__ __launch_bounds__(256) void pdsch_csimax_cols(const PdschJobDev* __re
     } else {
       csi_of(J, H, noise, c0, c1);
     }
-    b0 = max(b0, __float_as_uint(c0));
-    b1 = max(b1, __float_as_uint(c1));
+    b0 = max(b0, csi_key(c0));
+    b1 = max(b1, csi_key(c1));
   }
   __shared__ uint32_t red[2][4];
 #pragma unroll
@@ -877,7 +891,7 @@ __global__ __launch_bounds__(256) void pdsch_csimax_cols(const PdschJobDev* __re
   __syncthreads();
   if (threadIdx.x < 2) {
     const uint32_t l = threadIdx.x;
-    if (J.cw[l]) *gptr(J.cw[l]->cmax_final) = max(max(red[l][0], red[l][1]), max(red[l][2], red[l][3]));
+    if (J.cw[l]) *gptr(J.cw[l]->cmax_final) = csi_key_bits(max(max(red[l][0], red[l][1]), max(red[l][2], red[l][3])));
   }
 }
 

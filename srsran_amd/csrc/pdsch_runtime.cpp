@@ -198,6 +198,8 @@ struct mi355_pdsch {
   uint32_t                             last_map_hdr[10][4]{};
   uint8_t                              last_map_prb[10][2][MI355_MAX_PRB]{};
   std::unordered_map<uint32_t, uint32_t*> scr; // packed descrambling sequences per c_init (HBM)
+  // bounds of the two caches, checked once per call before planning (mi355_pdsch_debug_set_cache_limits)
+  uint32_t                             max_maps = 8192, max_scr = 4096;
   char*                                scratch = nullptr;
   size_t                               scratch_cap = 0;
   // outgrown scratch buffers and evicted extraction maps: freed at destroy (hipFree waits for the whole device, which
@@ -236,6 +238,21 @@ static int get_scratch(mi355_pdsch_t* q, size_t bytes, char** p)
   return MI355_SUCCESS;
 }
 
+// Bound the map cache, once per call and before any job of the batch is planned: a map handed to a job stays intact
+// until the next call on this receiver begins (the batch's front end and mi355_pdsch_debug_stage's on-demand
+// pdsch_eq_llr read it), so the bound is soft by one batch's distinct allocations.  The maps' last readers are the
+// front-end kernels of the previous batch (fe_done; the debug stage waits for its own kernel): once they are done the
+// buffers are reused for new maps, without a free (hipFree would wait for the whole device).
+static int trim_maps(mi355_pdsch_t* q)
+{
+  if (q->maps.size() < q->max_maps) return MI355_SUCCESS;
+  if (q->fe_armed) CHECK_HIP(wait_event(q->fe_done));
+  for (auto& kv : q->maps) q->map_free.emplace_back(kv.second.d, kv.second.bytes);
+  q->maps.clear();
+  for (auto& m : q->last_map) m = MapEntry{};
+  return MI355_SUCCESS;
+}
+
 static int get_map(mi355_pdsch_t* q, const mi355_pdsch_grant_t& g, uint32_t cfi, uint32_t sf, MapEntry* out)
 {
   // the jobs of a batch usually share the allocation: compare with the previous lookup of this subframe index first
@@ -254,14 +271,6 @@ static int get_map(mi355_pdsch_t* q, const mi355_pdsch_grant_t& g, uint32_t cfi,
   key.append((const char*)g.prb_idx[1], q->cell.nof_prb);
   auto it = q->maps.find(key);
   if (it == q->maps.end()) {
-    if (q->maps.size() >= 8192) { // bound the cache
-      // the maps' last readers are the front-end kernels of this object's previous batch (fe_done): once they are
-      // done the buffers are reused for new maps, without a free (hipFree would wait for the whole device)
-      if (q->fe_armed) CHECK_HIP(wait_event(q->fe_done));
-      for (auto& kv : q->maps) q->map_free.emplace_back(kv.second.d, kv.second.bytes);
-      q->maps.clear();
-      for (auto& m : q->last_map) m = MapEntry{};
-    }
     std::vector<uint16_t> idx;
     idx.reserve(14 * 12 * q->cell.nof_prb);
     walk_map(q->cell, g, cfi, sf, [&](uint32_t, uint32_t p) { idx.push_back((uint16_t)p); });
@@ -400,6 +409,15 @@ static int plan_job(mi355_pdsch_t* q, const mi355_pdsch_job_t& j, const mi355_pd
   return MI355_SUCCESS;
 }
 
+// estimates equal in every OFDM symbol (mi355_pdsch_set_ce_invariant): row 0 read, and the fused equaliser where the
+// csi depends on the subcarrier only (CDD alternates its precoder per RE, SFBC pairs REs)
+static void set_invariant(const mi355_pdsch_t* q, JobPlan& P, bool ce_invariant)
+{
+  P.dev.h_invariant = ce_invariant ? 1u : 0u;
+  P.dev.fused       = !q->llr8 && ce_invariant &&
+                        (P.dev.scheme == MI355_TXSCHEME_PORT0 || P.dev.scheme == MI355_TXSCHEME_SPATIALMUX) ? 1u : 0u;
+}
+
 // front-end over planned jobs; fills P.d_off/csi_off/e_off and runs kernels A and B on s
 static int run_frontend(mi355_pdsch_t* q, const mi355_pdsch_job_t* jobs, std::vector<JobPlan>& plans, hipStream_t s,
                         bool after_s = false, const EqRmPlan* er = nullptr)
@@ -410,7 +428,7 @@ static int run_frontend(mi355_pdsch_t* q, const mi355_pdsch_job_t* jobs, std::ve
   std::vector<PdschCwDev> cws;
   std::vector<uint32_t>   new_ci;
   std::vector<uint32_t*>  new_dst;
-  if (q->scr.size() > 4096) { // bound the sequence cache (~76 MB)
+  if (q->scr.size() > q->max_scr) { // bound the sequence cache (~76 MB at 4096)
     CHECK_HIP(hipStreamSynchronize(s));
     for (auto& kv : q->scr) (void)hipFree(kv.second);
     q->scr.clear();
@@ -665,11 +683,14 @@ int mi355_pdsch_frontend(mi355_pdsch_t* q, const mi355_pdsch_job_t* jobs, uint32
   CHECK_HIP(hipSetDevice(q->device));
   hipStream_t          s = stream ? (hipStream_t)stream : q->own;
   std::vector<JobPlan> plans(njobs);
+  int                  r = trim_maps(q);
+  if (r) return r;
   for (uint32_t i = 0; i < njobs; i++) {
-    int r = plan_job(q, jobs[i], nullptr, plans[i]);
+    r = plan_job(q, jobs[i], nullptr, plans[i]);
     if (r) return r;
+    set_invariant(q, plans[i], q->ce_inv);
   }
-  int r = run_frontend(q, jobs, plans, s);
+  r = run_frontend(q, jobs, plans, s);
   if (r) return r;
   CHECK_HIP(wait_stream(s));
   q->last = plans;
@@ -697,6 +718,23 @@ int mi355_pdsch_debug_stage(mi355_pdsch_t* q, uint32_t job, uint32_t cw, const f
       if (P.decode[t] && P.cw_of_tb[t] == cw)
         *e = q->llr8 ? (const int16_t*)((const int8_t*)q->e_arena + P.e_off[t]) : q->e_arena + P.e_off[t];
   }
+  return MI355_SUCCESS;
+}
+
+int mi355_pdsch_debug_set_cache_limits(mi355_pdsch_t* q, uint32_t max_maps, uint32_t max_scr)
+{
+  if (!q) return MI355_ERROR_INVALID_INPUTS;
+  std::lock_guard<std::mutex> lk(q->mu);
+  if (max_maps) q->max_maps = max_maps;
+  if (max_scr) q->max_scr = max_scr;
+  return MI355_SUCCESS;
+}
+
+int mi355_pdsch_debug_job_map(mi355_pdsch_t* q, uint32_t job, const uint16_t** d_map, uint32_t* n)
+{
+  if (!q || job >= q->last.size() || !d_map || !n) return MI355_ERROR_INVALID_INPUTS;
+  *d_map = q->last[job].dev.map;
+  *n     = q->last[job].dev.nof_re;
   return MI355_SUCCESS;
 }
 
@@ -858,20 +896,19 @@ int mi355::pdsch_decode_batch_dev_noise(mi355_pdsch_t* q, mi355_softbuffer_pool_
   CHECK_HIP(hipSetDevice(q->device));
   hipStream_t          s = stream ? (hipStream_t)stream : q->own;
   std::vector<JobPlan> plans(njobs);
+  int                  r = trim_maps(q);
+  if (r) return r;
   for (uint32_t i = 0; i < njobs; i++) {
-    int r = plan_job(q, jobs[i], &res[2 * i], plans[i]);
+    r = plan_job(q, jobs[i], &res[2 * i], plans[i]);
     if (r) return r;
     // noise estimate left in device memory by the channel estimator (ZF ignores it, pdsch.c:934)
     if (d_noise && jobs[i].cfg.decoder_type != MI355_MIMO_DECODER_ZF) plans[i].dev.noise_dev = d_noise + i;
-    plans[i].dev.h_invariant = ce_invariant ? 1u : 0u;
-    // csi depends on the subcarrier only for these schemes (CDD alternates its precoder per RE, SFBC pairs REs)
-    plans[i].dev.fused = !q->llr8 && ce_invariant && (plans[i].dev.scheme == MI355_TXSCHEME_PORT0 ||
-                                                      plans[i].dev.scheme == MI355_TXSCHEME_SPATIALMUX) ? 1u : 0u;
+    set_invariant(q, plans[i], ce_invariant);
   }
   EqRmPlan   er;
   const bool eqrm = plan_eq_rm(q, pool, jobs, plans, er);
   const auto t1   = now();
-  int        r    = run_frontend(q, jobs, plans, s, after_s, eqrm ? &er : nullptr);
+  r               = run_frontend(q, jobs, plans, s, after_s, eqrm ? &er : nullptr);
   if (r) return r;
   if (prof) {
     auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };

@@ -68,6 +68,9 @@ def _declare():
     L.mi355_pdsch_debug_stage.argtypes = [vp, u32, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.mi355_pdsch_set_llr_8bit.argtypes = [vp, C.c_int]
     L.mi355_pdsch_set_ce_invariant.argtypes = [vp, C.c_int]
+    L.mi355_pdsch_debug_set_cache_limits.argtypes = [vp, u32, u32]
+    L.mi355_pdsch_debug_job_map.argtypes = [vp, u32, C.POINTER(vp), C.POINTER(u32)]
+    L.mi355_pdsch_eqrm_profile.argtypes = [C.c_int, C.c_void_p]
     L.mi355_pdsch_re_map.restype = u32
     L.mi355_pdsch_re_map.argtypes = [C.POINTER(Cell), C.POINTER(PdschGrant), u32, u32, C.c_void_p]
     L._pdsch_declared = True
@@ -86,6 +89,14 @@ def re_map(cell: Cell, grant: PdschGrant, cfi: int, sf_idx: int) -> np.ndarray:
     idx = np.zeros(14 * 12 * cell.nof_prb, np.uint32)
     n = L.mi355_pdsch_re_map(C.byref(cell), C.byref(grant), cfi, sf_idx, idx.ctypes.data)
     return idx[:n].copy()
+
+
+def eqrm_profile(enable: bool) -> np.ndarray:
+    """mi355_pdsch_eqrm_profile: arm (zeroed) or disarm pdsch_eq_rm's counters; returns what they held while armed:
+    (workgroups, prologue, equaliser, rate-dematching shader cycles), zeros when they were not armed."""
+    out = np.zeros(4, np.uint64)
+    check(_declare().mi355_pdsch_eqrm_profile(int(enable), out.ctypes.data), "eqrm_profile")
+    return out
 
 
 def make_grant(cell: Cell, prb: np.ndarray, cfi: int, sf_idx: int, tx_scheme: int, nof_layers: int,
@@ -161,6 +172,20 @@ class Pdsch:
             ee = np.zeros(nof_bits, np.int8 if getattr(self, "llr8", False) else np.int16)
             check(L.mi355_memcpy_d2h(ee.ctypes.data, e.value, ee.nbytes), "d2h")
         return dd, cc, ee
+
+    def debug_set_cache_limits(self, max_maps: int = 0, max_scr: int = 0):
+        """Bounds of the RE-map and descrambling-sequence caches (0 keeps the current value); for tests."""
+        check(self.L.mi355_pdsch_debug_set_cache_limits(self.h, max_maps, max_scr), "debug_set_cache_limits")
+
+    def debug_job_map(self, job: int):
+        """(device pointer, uint16 grid indices downloaded from it) of the extraction map job `job` of the last call
+        was planned with."""
+        p, n = C.c_void_p(), C.c_uint32()
+        check(self.L.mi355_pdsch_debug_job_map(self.h, job, C.byref(p), C.byref(n)), "debug_job_map")
+        out = np.zeros(n.value, np.uint16)
+        if n.value:
+            check(lib().mi355_memcpy_d2h(out.ctypes.data, p.value, out.nbytes), "d2h")
+        return p.value, out
 
     def close(self):
         if getattr(self, "h", None):

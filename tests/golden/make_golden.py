@@ -34,6 +34,9 @@ Contents
                      as SHA-256 plus their first 64 values; the PDSCH RE -> grid map through the compiled prb_dl.c
                      primitives (oracle/ref/ref_prb.c) for 6-110 PRB x 1/2/4 ports x CFI 1-3 x subframes x FDD/TDD
                      (SHA-256 per case); and the estimator's smoothing filters from the compiled chest_common.c.
+  demod_extremes.npz (``make_golden.py demod_extremes``) srslte_demod_soft_demodulate_s and _b for every modulation
+                     on symbols with a per-symbol gain from {1, 40, 300, 3e5, 1e9, 0}: int16 / int8 saturation, the
+                     scalar tails' wrap and the x86 conversions' out-of-range result, n = 7, 16, 17, 100.
 """
 from __future__ import annotations
 
@@ -330,6 +333,49 @@ def gen_pdsch_stages(rng):
     print("pdsch_stages.npz:", data["demod_n"], "demod,", data["scr_n"], "scrambling,", k, "predecoding cases")
 
 
+EXTREME_GAINS = (1.0, 40.0, 300.0, 3e5, 1e9, 0.0)
+
+
+def gen_demod_extremes(rng):
+    """srslte_demod_soft_demodulate_s / _b on symbols whose scaled values saturate int16 / int8 (gains 40, 300),
+    wrap in the scalar tails, leave the int32 range of the x86 conversions (3e5 at the 16-bit scales only, 1e9 at
+    every scale) or are exactly zero: unit-variance complex Gaussians times a gain drawn per symbol, for symbol
+    counts with SIMD bodies, scalar tails and both."""
+    R = oracle.ref()
+    data = {}
+    k = 0
+    for qm in (1, 2, 4, 6, 8):
+        for n in (7, 16, 17, 100):
+            gain = rng.choice(np.array(EXTREME_GAINS), n)
+            sym = (gain * (rng.standard_normal(n) + 1j * rng.standard_normal(n)) / np.sqrt(2)).astype(np.complex64)
+            iq = np.ascontiguousarray(sym.view(np.float32))
+            s = np.zeros(qm * n, np.int16)
+            assert R.ref_demod_soft_s(qm, iq, s, n) == 0
+            b = np.zeros(qm * n + 64, np.int8)
+            assert R.ref_demod_soft_b(qm, iq, b, n) == 0
+            data[f"x{k}_qm"], data[f"x{k}_sym"] = np.int32(qm), sym
+            data[f"x{k}_llr_s"], data[f"x{k}_llr_b"] = s, b[: qm * n].copy()
+            k += 1
+    data["n"] = np.int32(k)
+    save_reproducible(os.path.join(OUT, "demod_extremes.npz"), data)
+    print("demod_extremes.npz:", k, "cases")
+
+
+def save_reproducible(path, data):
+    """An .npz as np.savez_compressed writes it, with a fixed time stamp on every entry: the same arrays give the
+    same bytes whenever the file is made."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for name, v in data.items():
+            raw = io.BytesIO()
+            np.lib.format.write_array(raw, np.asanyarray(v), allow_pickle=False)
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, raw.getvalue())
+
+
 PIN_N = 14400  # PDSCH REs of a full-allocation 100-PRB 2-port subframe, CFI 1, no PBCH / sync (sf 1)
 
 
@@ -524,6 +570,9 @@ def main():
     if sys.argv[1:] == ["tdec8"]:
         gen_tdec8(np.random.default_rng(8008))
         return
+    if sys.argv[1:] == ["demod_extremes"]:
+        gen_demod_extremes(np.random.default_rng(5005))
+        return
     rng = np.random.default_rng(20201010)
     gen_tdec_auto(rng)
     gen_tdec_generic(rng)
@@ -534,6 +583,7 @@ def main():
     gen_pdcch(np.random.default_rng(4004))
     gen_tdec8(np.random.default_rng(8008))
     gen_ref_pins()
+    gen_demod_extremes(np.random.default_rng(5005))
 
 
 if __name__ == "__main__":

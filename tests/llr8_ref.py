@@ -22,8 +22,20 @@ def abs8(v) -> np.ndarray:  # _mm_abs_epi8: |-128| = -128
     return np.where(v == -128, -128, np.abs(v))
 
 
+def cvt_i32(x) -> np.ndarray:
+    """cvt(t)ps2dq / cvtt(ss|sd)2si on an already rounded value: outside the int32 range the "integer indefinite"
+    INT32_MIN (pinned by tests/golden/demod_extremes.npz; finite inputs only)."""
+    x = np.asarray(x, np.float64)
+    ok = np.abs(x) < 2.0 ** 31
+    return np.where(ok, np.where(ok, x, 0.0), -2.0 ** 31).astype(np.int64)
+
+
 def trunc(x) -> np.ndarray:
-    return np.trunc(x).astype(np.int64)
+    return cvt_i32(np.trunc(x))
+
+
+def rint(x) -> np.ndarray:
+    return cvt_i32(np.rint(x))
 
 
 def demod_b(sym: np.ndarray, qm: int) -> np.ndarray:
@@ -32,7 +44,9 @@ def demod_b(sym: np.ndarray, qm: int) -> np.ndarray:
     re, im = sym.real.astype(F), sym.imag.astype(F)
     body = np.arange(n) < n // 8 * 8
     out = np.zeros((n, qm), np.int64)
-    if qm == 2:  # srslte_vec_convert_fb: truncation, saturating packs (SIMD body) / wrap (scalar tail)
+    if qm == 1:  # demod_bpsk_lte_b: float sum times the double M_SQRT1_2
+        out[:, 0] = wrap8(trunc((F(-20.0) * (re + im)).astype(np.float64) * np.sqrt(0.5)))
+    elif qm == 2:  # srslte_vec_convert_fb: truncation, saturating packs (SIMD body) / wrap (scalar tail)
         s = F(-20 * np.sqrt(2.0))
         for k, x in enumerate((re, im)):
             t = trunc(x * s)
@@ -40,13 +54,13 @@ def demod_b(sym: np.ndarray, qm: int) -> np.ndarray:
     elif qm == 4:
         kq = F(60) / np.sqrt(F(10))
         for k, x in enumerate((re, im)):
-            sb = sat8(np.rint(x * F(-30.0)))
+            sb = sat8(rint(x * F(-30.0)))
             y = wrap8(trunc(F(30.0) * x))
             out[:, k] = np.where(body, sb, wrap8(-y))
             out[:, 2 + k] = np.where(body, wrap8(abs8(sb) - 18), wrap8(trunc(np.abs(y).astype(F) - kq)))
     elif qm == 6:
         for k, x in enumerate((re, im)):
-            sb = sat8(np.rint(x * F(-40.0)))
+            sb = sat8(rint(x * F(-40.0)))
             a1 = wrap8(abs8(sb) - 24)
             y = wrap8(trunc(F(40.0) * x))
             t1 = wrap8(wrap8(np.abs(y)) - 24)

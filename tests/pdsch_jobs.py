@@ -157,6 +157,20 @@ def softbuffer_check(rx, sb: int, e_o: np.ndarray, tbs: int, qm: int, rv: int, w
     """The decoder buffers of softbuffer sb after a fresh-buffer decode (rate dematched by pdsch_eq_rm or
     dlsch_rm_rx) equal the oracle's rate dematching of the oracle's LLRs (orc_dlsch_rm_tb: rm_turbo_rx_lut into
     zeroed buffers), bit for bit over each code block's systematic, parity and tail positions."""
+    import oracle
+    seg = np.zeros(6, np.uint32)
+    oracle.lib().orc_cbsegm(tbs, seg)
+    Cn = int(seg[0])
+    want = np.zeros(Cn * 18600, np.int16)
+    e = np.ascontiguousarray(e_o, np.int16)
+    assert oracle.lib().orc_dlsch_rm_tb(e, e.size, tbs, qm, rv, want, 18600) == Cn
+    pool_softbuffer_check(rx.pool, sb, want, tbs, what)
+
+
+def pool_softbuffer_check(pool, sb: int, want: np.ndarray, tbs: int, what=None):
+    """The decoder buffers of softbuffer sb of a SoftbufferPool equal want (code block c at want[c * 18600:], the
+    layout of oracle.Softbuffer.buf and orc_dlsch_rm_tb), bit for bit over each code block's systematic, parity and
+    tail positions."""
     import ctypes as C
     import oracle
     from srsran_amd import lib
@@ -164,14 +178,12 @@ def softbuffer_check(rx, sb: int, e_o: np.ndarray, tbs: int, qm: int, rv: int, w
     buf, stride, mcb = C.POINTER(C.c_int16)(), C.c_uint32(), C.c_uint32()
     L.mi355_softbuffer_pool_buffer.argtypes = [C.c_void_p, C.POINTER(C.POINTER(C.c_int16)), C.POINTER(C.c_uint32),
                                                C.POINTER(C.c_uint32)]
-    assert L.mi355_softbuffer_pool_buffer(rx.pool.h, C.byref(buf), C.byref(stride), C.byref(mcb)) == 0
-    rx.pool.materialize(sb, 1)  # unwritten empty parity rows of fresh buffers -> the zeros they stand for
+    assert L.mi355_softbuffer_pool_buffer(pool.h, C.byref(buf), C.byref(stride), C.byref(mcb)) == 0
+    pool.materialize(sb, 1)  # unwritten empty parity rows of fresh buffers -> the zeros they stand for
     seg = np.zeros(6, np.uint32)
     oracle.lib().orc_cbsegm(tbs, seg)
     Cn = int(seg[0])
-    want = np.zeros(Cn * 18600, np.int16)
-    e = np.ascontiguousarray(e_o, np.int16)
-    assert oracle.lib().orc_dlsch_rm_tb(e, e.size, tbs, qm, rv, want, 18600) == Cn
+    want = np.ascontiguousarray(want, np.int16).reshape(-1)
     got = np.zeros((Cn, stride.value), np.int16)
     base = C.cast(buf, C.c_void_p).value + 2 * sb * mcb.value * stride.value
     L.mi355_memcpy_d2h(got.ctypes.data, base, got.nbytes)

@@ -34,6 +34,23 @@ def test_demod_golden(g):
         np.testing.assert_array_equal(got, g[f"demod{k}_llr"], err_msg=f"case {k} qm={qm}")
 
 
+def test_demod_extremes_golden():
+    """Both demapper checkers where the GPU front end is compared at saturating inputs (test_pdsch_extremes_gpu.py):
+    oracle.demod_soft_s and tests/llr8_ref.demod_b equal the compiled reference bit for bit on symbols with a
+    per-symbol gain from {1, 40, 300, 3e5, 1e9, 0} -- int16 / int8 saturation in the SIMD bodies, wrap in the scalar
+    tails, and the x86 conversions' INT32_MIN for values outside int32 (tests/golden/demod_extremes.npz)."""
+    from tests import llr8_ref
+    z = np.load(os.path.join(os.path.dirname(GOLD), "demod_extremes.npz"))
+    assert int(z["n"]) == 20
+    big = 0
+    for k in range(int(z["n"])):
+        qm, sym = int(z[f"x{k}_qm"]), z[f"x{k}_sym"]
+        big += int((np.abs(sym.view(np.float32)) * 20 >= 2.0 ** 31).sum())
+        np.testing.assert_array_equal(oracle.demod_soft_s(qm, sym), z[f"x{k}_llr_s"], err_msg=f"16-bit {k} qm={qm}")
+        np.testing.assert_array_equal(llr8_ref.demod_b(sym, qm), z[f"x{k}_llr_b"], err_msg=f"8-bit {k} qm={qm}")
+    assert big > 50  # components beyond int32 at the smallest (8-bit QPSK) scale
+
+
 def test_scrambling_golden(g):
     for k in range(int(g["scr_n"])):
         got = oracle.scramble_s(int(g[f"scr{k}_cinit"]), g[f"scr{k}_in"])
