@@ -13,15 +13,7 @@
 #include "../../include/srsran_amd/channel.h"
 #include "../../include/srsran_amd/tdec.h"
 #include "channel_internal.h"
-
-#define CHECK_HIP(x)                                                                                                   \
-  do {                                                                                                                 \
-    hipError_t e_ = (x);                                                                                               \
-    if (e_ != hipSuccess) {                                                                                            \
-      fprintf(stderr, "[srsran_amd] %s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_));                 \
-      return MI355_ERROR;                                                                                              \
-    }                                                                                                                  \
-  } while (0)
+#include "device_mem.h"
 
 using namespace mi355;
 

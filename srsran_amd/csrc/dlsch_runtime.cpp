@@ -20,6 +20,7 @@
 
 #include "../../include/srsran_amd/dlsch.h"
 #include "../../include/srsran_amd/tdec.h"
+#include "device_mem.h"
 #include "dlsch_internal.h"
 #include "host_staging.h"
 #include "tdec8_internal.h"
@@ -30,15 +31,6 @@
 
 using namespace mi355;
 
-#define CHECK_HIP(x)                                                                                                   \
-  do {                                                                                                                 \
-    hipError_t e_ = (x);                                                                                               \
-    if (e_ != hipSuccess) {                                                                                            \
-      fprintf(stderr, "[srsran_amd] %s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_));                 \
-      return MI355_ERROR;                                                                                              \
-    }                                                                                                                  \
-  } while (0)
-
 struct mi355_softbuffer_pool {
   int      device = 0;
   uint32_t nof_sb = 0, max_cb = 0;
@@ -48,7 +40,7 @@ struct mi355_softbuffer_pool {
   uint8_t* fresh  = nullptr; // nof_sb * max_cb: buffer logically zero (lazy reset)
   // batched reset lists {softbuffer, code blocks to reset}, two in turn: a call's list upload waits only for the
   // reset kernel that read the same buffer two calls ago (ev_list), not for everything queued before it
-  uint2*     d_list[2]   = {nullptr, nullptr};
+  mi355::DevMem d_list[2]; // uint2
   uint32_t   list_cap[2] = {0, 0};
   hipEvent_t ev_list[2]  = {nullptr, nullptr};
   bool       ev_armed[2] = {false, false};
@@ -88,23 +80,21 @@ struct mi355_dlsch {
   hipStream_t                            own    = nullptr;
   uint32_t                               max_its = 10; // SRSLTE_PDSCH_MAX_TDEC_ITERS, sch.c:35
   std::map<uint32_t, mi355_tdec_batch_t*> dec;         // one decoder workspace per K
-  std::map<uint64_t, uint16_t*>          rm;           // (K << 2 | rv) -> device table
-  std::map<uint64_t, uint16_t*>          rm8;          // the same for the 8-bit decoder layout
+  DevCache<uint64_t>                     rm;           // (K << 2 | rv) -> device table (uint16_t)
+  DevCache<uint64_t>                     rm8;          // the same for the 8-bit decoder layout
   struct Compact {
-    uint16_t* d;
-    uint32_t  nq, qoff;
+    DevMem   d; // uint16_t
+    uint32_t nq = 0, qoff = 0;
   };
-  std::map<uint64_t, Compact>            rmc;          // (K, rv, E) -> compact image table (dlsch_rm_compact)
+  DevCache<uint64_t, Compact>            rmc;          // (K, rv, E) -> compact image table (dlsch_rm_compact)
   std::map<uint32_t, mi355_tdec8_t*>     dec8;         // 8-bit decoder workspace per K
-  std::map<uint32_t, uint32_t*>          scales;       // K -> per-lane CRC scale factors
-  std::map<uint32_t, uint32_t*>          tb_scales;    // TB bytes -> per-thread CRC24A scale factors (epilogue)
-  CrcTable*                              crc = nullptr; // [0] CRC24A, [1] CRC24B
+  DevCache<uint32_t>                     scales;       // K -> per-lane CRC scale factors (uint32_t)
+  DevCache<uint32_t>                     tb_scales;    // TB bytes -> per-thread CRC24A scale factors (epilogue)
+  DevMem                                 crc;          // CrcTable [0] CRC24A, [1] CRC24B
   // per-call scratch, two in turn: a call's descriptor upload waits only for the epilogue of the call before last
   // (done_ev of the same slot, the last reader of its staged part), so a batch enqueued behind one still in flight
   // (find_and_decode's second chunk) uploads at once instead of at the first one's end
-  char*      scratch[2]     = {nullptr, nullptr};
-  size_t     scratch_cap[2] = {0, 0};
-  std::vector<void*> retired; // outgrown scratch, freed at destroy (hipFree waits for the whole device)
+  DevScratch scratch[2];
   hipEvent_t done_ev[2]     = {nullptr, nullptr};
   bool       done_armed[2]  = {false, false};
   uint32_t   par            = 0;
@@ -206,8 +196,8 @@ static uint32_t rm_buflen(uint32_t K) { return tdec_subblocks(K) ? 3 * (K + 32) 
 static int rm_table(mi355_dlsch_t* q, uint32_t K, uint32_t rv, const uint16_t** out)
 {
   const uint64_t key = ((uint64_t)K << 2) | rv;
-  auto           it  = q->rm.find(key);
-  if (it == q->rm.end()) {
+  DevMem*        m   = nullptr;
+  int            e   = q->rm.get(key, &m, [&](DevMem& d) -> int {
     const std::vector<uint16_t> t = rm_rx_table(K, rv);
     const uint32_t              buflen = rm_buflen(K);
     std::vector<uint16_t>       inv(rm_rowmin_off(buflen) + rm_rowmin_len(), 0);
@@ -223,32 +213,28 @@ static int rm_table(mi355_dlsch_t* q, uint32_t K, uint32_t rv, const uint16_t** 
           rmin[s * 32 * SB_ROWMASK_WORDS + j] = m; // rows >= L stay 0 (defined)
         }
     }
-    uint16_t* d = nullptr;
-    CHECK_HIP(hipMalloc(&d, inv.size() * 2));
-    CHECK_HIP(hipMemcpy(d, inv.data(), inv.size() * 2, hipMemcpyHostToDevice));
-    it = q->rm.emplace(key, d).first;
-  }
-  *out = it->second;
-  return MI355_SUCCESS;
+    CHECK_HIP(d.upload(inv));
+    return MI355_SUCCESS;
+  });
+  if (!e) *out = m->as<uint16_t>();
+  return e;
 }
 
 // the same for the 8-bit decoder buffer layout (srslte_rm_turbo_rx_lut_8bit: sub-blocks of the 8-bit decoder)
 static int rm8_table(mi355_dlsch_t* q, uint32_t K, uint32_t rv, const uint16_t** out)
 {
   const uint64_t key = ((uint64_t)K << 2) | rv;
-  auto           it  = q->rm8.find(key);
-  if (it == q->rm8.end()) {
+  DevMem*        m   = nullptr;
+  int            e   = q->rm8.get(key, &m, [&](DevMem& d) -> int {
     const uint32_t              nsb = tdec_subblocks_8bit(K);
     const std::vector<uint16_t> t   = rm_rx_table_nsb(K, rv, nsb);
     std::vector<uint16_t>       inv((nsb ? 3 * (K + 32) + 12 : 3 * K + 12) + 1, RM_NONE);
     for (size_t r = 0; r < t.size(); r++) inv[t[r]] = (uint16_t)r;
-    uint16_t* d = nullptr;
-    CHECK_HIP(hipMalloc(&d, inv.size() * 2));
-    CHECK_HIP(hipMemcpy(d, inv.data(), inv.size() * 2, hipMemcpyHostToDevice));
-    it = q->rm8.emplace(key, d).first;
-  }
-  *out = it->second;
-  return MI355_SUCCESS;
+    CHECK_HIP(d.upload(inv));
+    return MI355_SUCCESS;
+  });
+  if (!e) *out = m->as<uint16_t>();
+  return e;
 }
 
 static uint32_t gf2_mulmod24_host(uint32_t a, uint32_t b, uint32_t poly)
@@ -262,39 +248,40 @@ static uint32_t gf2_mulmod24_host(uint32_t a, uint32_t b, uint32_t poly)
   return r & 0xffffffu;
 }
 
+// x^(8 n) mod P by square and multiply
+static uint32_t gf2_xpow8(uint32_t n, uint32_t poly)
+{
+  uint32_t sc = 1, x8 = 1u << 8; // x^(8 * 2^i)
+  for (; n; n >>= 1) {
+    if (n & 1) sc = gf2_mulmod24_host(sc, x8, poly);
+    x8 = gf2_mulmod24_host(x8, x8, poly);
+  }
+  return sc;
+}
+
 // per-lane CRC chunk scale factors for the decision bytes of K (wave_crc24_scaled), both polynomials
 static int crc_scales(mi355_dlsch_t* q, uint32_t K, const uint32_t** out)
 {
-  auto it = q->scales.find(K);
-  if (it == q->scales.end()) {
+  DevMem* m = nullptr;
+  int     e = q->scales.get(K, &m, [&](DevMem& d) -> int {
     // [0, 128): 64 lanes of a wave (dlsch_cb_check); [128, 144): the NL = nsb / 2 lanes of a code block in the
     // window decoder's fused check (tdec_kernels.hip), 8 per polynomial
     std::vector<uint32_t> t(144, 0u);
     const uint32_t        nbytes = K / 8, chunk = (nbytes + 63) / 64;
     const uint32_t        polys[2] = {0x1864CFB, 0x1800063};
-    auto                  xpow = [](uint32_t after, uint32_t poly) { // x^(8 * after) mod P
-      uint32_t sc = 1, x8 = 1u << 8; // x^(8 * 2^i)
-      for (; after; after >>= 1) {
-        if (after & 1) sc = gf2_mulmod24_host(sc, x8, poly);
-        x8 = gf2_mulmod24_host(x8, x8, poly);
-      }
-      return sc;
-    };
     const uint32_t nl = std::max(1u, mi355_tdec_autoimp_get_subblocks(K) / 2), cl = nbytes / nl;
     for (int pi = 0; pi < 2; pi++) {
       for (uint32_t lane = 0; lane < 64; lane++) {
         const uint32_t b0 = std::min(nbytes, lane * chunk), b1 = std::min(nbytes, b0 + chunk);
-        t[pi * 64 + lane] = xpow(nbytes - b1, polys[pi]);
+        t[pi * 64 + lane] = gf2_xpow8(nbytes - b1, polys[pi]);
       }
-      for (uint32_t l = 0; l < nl && l < 8; l++) t[128 + 8 * pi + l] = xpow(nbytes - (l + 1) * cl, polys[pi]);
+      for (uint32_t l = 0; l < nl && l < 8; l++) t[128 + 8 * pi + l] = gf2_xpow8(nbytes - (l + 1) * cl, polys[pi]);
     }
-    uint32_t* d = nullptr;
-    CHECK_HIP(hipMalloc(&d, t.size() * 4));
-    CHECK_HIP(hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-    it = q->scales.emplace(K, d).first;
-  }
-  *out = it->second;
-  return MI355_SUCCESS;
+    CHECK_HIP(d.upload(t));
+    return MI355_SUCCESS;
+  });
+  if (!e) *out = m->as<uint32_t>();
+  return e;
 }
 
 // the TB epilogue's CRC24A of nbytes bytes by 256 threads (block_crc24_scaled4): thread t's factor
@@ -304,41 +291,28 @@ static int crc_scales(mi355_dlsch_t* q, uint32_t K, const uint32_t** out)
 // distinct sizes 190 KB).
 static int tb_crc_scales(mi355_dlsch_t* q, uint32_t nbytes, const uint32_t** out)
 {
-  auto it = q->tb_scales.find(nbytes);
-  if (it == q->tb_scales.end()) {
+  DevMem* m = nullptr;
+  int     e = q->tb_scales.get(nbytes, &m, [&](DevMem& d) -> int {
     std::vector<uint32_t> t(256);
     const uint32_t        chunk = ((nbytes + 255) / 256 + 3) / 4 * 4, poly = 0x1864CFB;
     for (uint32_t tid = 0; tid < 256; tid++) {
       const uint32_t b0 = std::min(nbytes, tid * chunk), b1 = std::min(nbytes, b0 + chunk);
-      uint32_t       sc = 1, x8 = 1u << 8; // x^(8 * 2^i)
-      for (uint32_t after = nbytes - b1; after; after >>= 1) {
-        if (after & 1) sc = gf2_mulmod24_host(sc, x8, poly);
-        x8 = gf2_mulmod24_host(x8, x8, poly);
-      }
-      t[tid] = sc;
+      t[tid] = gf2_xpow8(nbytes - b1, poly);
     }
-    uint32_t* d = nullptr;
-    CHECK_HIP(hipMalloc(&d, t.size() * 4));
-    CHECK_HIP(hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-    it = q->tb_scales.emplace(nbytes, d).first;
-  }
-  *out = it->second;
-  return MI355_SUCCESS;
+    CHECK_HIP(d.upload(t));
+    return MI355_SUCCESS;
+  });
+  if (!e) *out = m->as<uint32_t>();
+  return e;
 }
 
 static int scratch(mi355_dlsch_t* q, uint32_t k, size_t bytes, char** p)
 {
-  if (bytes > q->scratch_cap[k]) {
-    if (q->scratch[k]) { // may still be read by this object's batch in flight: retired, not freed
-      q->retired.push_back(q->scratch[k]);
-      q->scratch[k]    = nullptr;
-      q->done_armed[k] = false;
-    }
-    size_t cap = bytes + bytes / 4 + 4096;
-    CHECK_HIP(hipMalloc(&q->scratch[k], cap));
-    q->scratch_cap[k] = cap;
-  }
-  *p = q->scratch[k];
+  // an outgrown buffer may still be read by this object's batch in flight: retired, not freed
+  bool grew = false;
+  CHECK_HIP(q->scratch[k].reserve(bytes, bytes + bytes / 4 + 4096, DevScratch::Retire, &grew));
+  if (grew) q->done_armed[k] = false;
+  *p = q->scratch[k].base();
   return MI355_SUCCESS;
 }
 
@@ -376,7 +350,6 @@ void mi355_softbuffer_pool_destroy(mi355_softbuffer_pool_t* p)
   for (int k = 0; k < 2; k++) {
     if (p->ev_armed[k]) (void)hipEventSynchronize(p->ev_list[k]);
     if (p->ev_list[k]) (void)hipEventDestroy(p->ev_list[k]);
-    (void)hipFree(p->d_list[k]);
   }
   delete p;
 }
@@ -414,13 +387,10 @@ int mi355_softbuffer_reset_tbs_batch(mi355_softbuffer_pool_t* p, const uint32_t*
   const uint32_t k = p->lpar;
   p->lpar ^= 1u;
   if (n > p->list_cap[k]) {
-    if (p->d_list[k]) {
-      if (p->ev_armed[k]) CHECK_HIP(hipEventSynchronize(p->ev_list[k]));
-      CHECK_HIP(hipFree(p->d_list[k]));
-      p->ev_armed[k] = false;
-    }
+    if (p->ev_armed[k]) CHECK_HIP(hipEventSynchronize(p->ev_list[k]));
+    p->ev_armed[k] = false;
     p->list_cap[k] = n + n / 2 + 64;
-    CHECK_HIP(hipMalloc(&p->d_list[k], p->list_cap[k] * sizeof(uint2)));
+    CHECK_HIP(p->d_list[k].alloc(p->list_cap[k] * sizeof(uint2))); // (frees the list this one outgrew)
   }
   if (!p->ev_list[k]) CHECK_HIP(hipEventCreateWithFlags(&p->ev_list[k], hipEventDisableTiming));
   CHECK_HIP(p->st_list.reserve(n * sizeof(uint2)));
@@ -430,8 +400,8 @@ int mi355_softbuffer_reset_tbs_batch(mi355_softbuffer_pool_t* p, const uint32_t*
     l[i] = make_uint2(sbs[i], std::min((tbs[i] + 24) / (6144 - 24) + 1, p->max_cb)); // softbuffer.c:128-132
   }
   // list buffer k was last read by the reset kernel of the call before last: the copy waits for that one only
-  CHECK_HIP(p->st_list.upload(p->d_list[k], s, false, p->ev_armed[k] ? p->ev_list[k] : nullptr));
-  CHECK_HIP(dlsch_launch_reset_list(p->d_list[k], n, p->max_cb, p->fresh, p->cb_crc, s));
+  CHECK_HIP(p->st_list.upload(p->d_list[k].p, s, false, p->ev_armed[k] ? p->ev_list[k] : nullptr));
+  CHECK_HIP(dlsch_launch_reset_list(p->d_list[k].as<uint2>(), n, p->max_cb, p->fresh, p->cb_crc, s));
   CHECK_HIP(hipEventRecord(p->ev_list[k], s));
   p->ev_armed[k] = true;
   if (!s) CHECK_HIP(hipStreamSynchronize(nullptr)); // (dlsch.h: NULL = done on return)
@@ -519,13 +489,9 @@ int mi355_dlsch_create(mi355_dlsch_t** q, int device)
   CHECK_HIP(hipSetDevice(device));
   auto* d   = new mi355_dlsch;
   d->device = device;
-  if (hipStreamCreateWithFlags(&d->own, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc(&d->crc, 2 * sizeof(CrcTable)) != hipSuccess) {
-    mi355_dlsch_destroy(d);
-    return MI355_ERROR;
-  }
   const CrcTable t[2] = {make_crc_table(0x1864CFB), make_crc_table(0x1800063)}; // CRC24A, CRC24B (crc.h:40-41)
-  if (hipMemcpy(d->crc, t, sizeof(t), hipMemcpyHostToDevice) != hipSuccess) {
+  if (hipStreamCreateWithFlags(&d->own, hipStreamNonBlocking) != hipSuccess ||
+      d->crc.upload(t, sizeof(t)) != hipSuccess) {
     mi355_dlsch_destroy(d);
     return MI355_ERROR;
   }
@@ -539,18 +505,9 @@ void mi355_dlsch_destroy(mi355_dlsch_t* q)
   (void)hipSetDevice(q->device);
   (void)hipDeviceSynchronize();
   for (auto& kv : q->dec) mi355_tdec_batch_destroy(kv.second);
-  for (auto& kv : q->rm) (void)hipFree(kv.second);
-  for (auto& kv : q->rm8) (void)hipFree(kv.second);
-  for (auto& kv : q->rmc) (void)hipFree(kv.second.d);
   for (auto& kv : q->dec8) mi355_tdec8_destroy(kv.second);
-  for (auto& kv : q->scales) (void)hipFree(kv.second);
-  for (auto& kv : q->tb_scales) (void)hipFree(kv.second);
-  (void)hipFree(q->crc);
-  for (void* r : q->retired) (void)hipFree(r);
-  for (int k = 0; k < 2; k++) {
-    (void)hipFree(q->scratch[k]);
+  for (int k = 0; k < 2; k++)
     if (q->done_ev[k]) (void)hipEventDestroy(q->done_ev[k]);
-  }
   if (q->own) (void)hipStreamDestroy(q->own);
   delete q;
 }
@@ -671,8 +628,8 @@ int mi355::dlsch_rm_compact(mi355_dlsch_t* q, uint32_t K, uint32_t rv, uint32_t 
   std::lock_guard<std::mutex> lock(q->mu);
   CHECK_HIP(hipSetDevice(q->device));
   const uint64_t key = ((((uint64_t)K << 2) | rv) << 16) | E;
-  auto           it  = q->rmc.find(key);
-  if (it == q->rmc.end()) {
+  mi355_dlsch::Compact* c = nullptr;
+  int e = q->rmc.get(key, &c, [&](mi355_dlsch::Compact& ent) -> int {
     const std::vector<uint16_t> t      = rm_rx_table(K, rv); // circular index r -> decoder position
     const uint32_t              buflen = rm_buflen(K), nquad = (buflen + 7) / 8;
     std::vector<uint16_t>       inv(buflen, (uint16_t)RM_NONE);
@@ -707,15 +664,14 @@ int mi355::dlsch_rm_compact(mi355_dlsch_t* q, uint32_t K, uint32_t rv, uint32_t 
       all[r] = (uint16_t)(8 * rank[pos / 8] + pos % 8);
     }
     memcpy(all.data() + off, qlist.data(), qlist.size() * 4);
-    uint16_t* d = nullptr;
-    CHECK_HIP(hipMalloc(&d, all.size() * 2));
-    CHECK_HIP(hipMemcpy(d, all.data(), all.size() * 2, hipMemcpyHostToDevice));
-    CHECK_HIP(hipStreamSynchronize(nullptr)); // (pageable source: landed before a non-blocking stream reads it)
-    it = q->rmc.emplace(key, mi355_dlsch::Compact{d, (uint32_t)qlist.size(), off}).first;
-  }
-  *tab  = it->second.d;
-  *nq   = it->second.nq;
-  *qoff = it->second.qoff;
+    CHECK_HIP(ent.d.upload(all));
+    ent.nq = (uint32_t)qlist.size(), ent.qoff = off;
+    return MI355_SUCCESS;
+  });
+  if (e) return e;
+  *tab  = c->d.as<uint16_t>();
+  *nq   = c->nq;
+  *qoff = c->qoff;
   return MI355_SUCCESS;
 }
 
@@ -863,7 +819,8 @@ int mi355::dlsch_decode_dev_hook(mi355_dlsch_t* q, mi355_softbuffer_pool_t* pool
   // part, is done at done_ev[slot]; a slot never used (or just reallocated) needs no wait
   CHECK_HIP(q->stage.upload(base, s, false, after_s && q->done_armed[slot] ? q->done_ev[slot] : nullptr));
 
-  DlschTbArgs ta{d_tb,  (int)ntb, d_data, pool->cb_crc, pool->data, d_ret, &q->crc[0],
+  const CrcTable* crc = q->crc.as<CrcTable>();
+  DlschTbArgs ta{d_tb,  (int)ntb, d_data, pool->cb_crc, pool->data, d_ret, &crc[0],
                  d_cb,  d_slot,   d_its,  d_done,       d_run,      d_avg};
   CHECK_HIP(dlsch_launch_prologue(ta, s));
 
@@ -966,7 +923,7 @@ int mi355::dlsch_decode_dev_hook(mi355_dlsch_t* q, mi355_softbuffer_pool_t* pool
       if ((r = mi355_tdec_win_tables(lv.td, lv.K, &la.dstE, &la.dstA))) return r;
       la.done    = d_done + lv.off;
       la.chk     = DlschCheckArgs{d_cb + lv.off, (int)lv.n, lv.K, 0, q->max_its, lv.dec, lv.K / 8, d_data, d_done + lv.off,
-                              d_run, d_run + 1, d_its + lv.off, pool->cb_crc, &q->crc[0], &q->crc[1], lv.scale};
+                              d_run, d_run + 1, d_its + lv.off, pool->cb_crc, &crc[0], &crc[1], lv.scale};
       la.prof    = g_lat_prof.load();
       la.ncb     = (int)lv.n;
       la.K       = (int)lv.K;
@@ -990,7 +947,7 @@ int mi355::dlsch_decode_dev_hook(mi355_dlsch_t* q, mi355_softbuffer_pool_t* pool
         if ((r = tdec8_halfit_batch(lv.t8, b, h, lv.dec, lv.K / 8, s))) return r;
       }
       DlschCheckArgs ca{d_cb + lv.off, (int)lv.n, lv.K, h, q->max_its, lv.dec, lv.K / 8, d_data,
-                        d_done + lv.off, d_run + h, d_run + h + 1, d_its + lv.off, pool->cb_crc, &q->crc[0], &q->crc[1],
+                        d_done + lv.off, d_run + h, d_run + h + 1, d_its + lv.off, pool->cb_crc, &crc[0], &crc[1],
                         lv.scale};
       bool fused = false; // the window decoder's decision-byte launches run the check in their epilogue
       if (!lv.t8) {

@@ -18,6 +18,7 @@
 
 #include "../../include/srsran_amd/enb_dl.h"
 #include "../../include/srsran_amd/tdec.h"
+#include "device_mem.h"
 #include "enb_dl_internal.h"
 #include "host_staging.h"
 #include "lte_common.h"
@@ -27,15 +28,6 @@
 #include "ue_dl_internal.h"
 
 using namespace mi355;
-
-#define CHECK_HIP(x)                                                                                                   \
-  do {                                                                                                                 \
-    hipError_t e_ = (x);                                                                                               \
-    if (e_ != hipSuccess) {                                                                                            \
-      fprintf(stderr, "[srsran_amd] %s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_));                 \
-      return MI355_ERROR;                                                                                              \
-    }                                                                                                                  \
-  } while (0)
 
 namespace {
 
@@ -52,8 +44,8 @@ uint32_t qm_of(uint32_t mod)
 }
 
 struct MapRef {
-  uint16_t* d = nullptr;
-  uint32_t  n = 0;
+  DevMem   d; // uint16_t
+  uint32_t n = 0;
 };
 
 } // namespace
@@ -62,34 +54,24 @@ struct mi355_enb_dl {
   int                              device = 0;
   mi355_cell_t                     cell{};
   hipStream_t                      own    = nullptr;
-  CrcTable*                        crc    = nullptr; // [0] CRC24A, [1] CRC24B
-  uint32_t*                        gold   = nullptr;
-  float2*                          pilots = nullptr;
-  float2*                          tw     = nullptr;
+  DevMem                           crc;    // CrcTable [0] CRC24A, [1] CRC24B
+  DevMem                           gold;   // uint32_t
+  DevMem                           pilots; // float2
+  DevMem                           tw;     // float2
   OfdmArgs                         ofdm{};
-  std::map<uint32_t, uint32_t*>    scr;  // packed scrambling sequences per c_init
-  std::map<uint32_t, uint16_t*>    txt;  // (K << 2 | rv) -> rate-matching selection table
-  std::map<uint32_t, uint16_t*>    qpp;  // K -> QPP interleaver table
-  std::map<std::string, MapRef>    maps; // RE maps
-  char*                            scratch     = nullptr;
-  size_t                           scratch_cap = 0;
+  DevCache<uint32_t>               scr;  // packed scrambling sequences per c_init
+  DevCache<uint32_t>               txt;  // (K << 2 | rv) -> rate-matching selection table
+  DevCache<uint32_t>               qpp;  // K -> QPP interleaver table
+  DevCache<std::string, MapRef>    maps; // RE maps
+  DevScratch                       scratch;
   HostStaging                      st;
   std::mutex                       mu;
 };
 
 static int get_scratch(mi355_enb_dl_t* q, size_t bytes, char** p)
 {
-  if (bytes > q->scratch_cap) {
-    if (q->scratch) {
-      CHECK_HIP(hipDeviceSynchronize());
-      CHECK_HIP(hipFree(q->scratch));
-      q->scratch = nullptr;
-    }
-    const size_t cap = bytes + bytes / 4 + 4096;
-    CHECK_HIP(hipMalloc(&q->scratch, cap));
-    q->scratch_cap = cap;
-  }
-  *p = q->scratch;
+  CHECK_HIP(q->scratch.reserve(bytes, bytes + bytes / 4 + 4096, DevScratch::SyncFree));
+  *p = q->scratch.base();
   return MI355_SUCCESS;
 }
 
@@ -108,64 +90,54 @@ static int upload_on(HostStaging& st, void* dst, hipStream_t s)
 static int get_txt(mi355_enb_dl_t* q, uint32_t K, uint32_t rv, const uint16_t** out)
 {
   const uint32_t key = (K << 2) | (rv & 3u);
-  auto           it  = q->txt.find(key);
-  if (it == q->txt.end()) {
+  DevMem*        m   = nullptr;
+  int            r   = q->txt.get(key, &m, [&](DevMem& d) -> int {
     std::vector<uint16_t> t = rm_tx_table(K, rv & 3u);
     for (auto& v : t) // encoder index 3m + s (tails 3K + j) -> stream << 14 | position
       v = v < 3 * K ? (uint16_t)(((v % 3u) << 14) | (v / 3u)) : (uint16_t)((3u << 14) | (v - 3 * K));
-    uint16_t* d = nullptr;
-    CHECK_HIP(hipMalloc(&d, t.size() * 2));
-    CHECK_HIP(hipMemcpy(d, t.data(), t.size() * 2, hipMemcpyHostToDevice));
-    it = q->txt.emplace(key, d).first;
-  }
-  *out = it->second;
-  return MI355_SUCCESS;
+    CHECK_HIP(d.upload(t));
+    return MI355_SUCCESS;
+  });
+  if (!r) *out = m->as<uint16_t>();
+  return r;
 }
 
 static int get_qpp(mi355_enb_dl_t* q, uint32_t K, const uint16_t** out)
 {
-  auto it = q->qpp.find(K);
-  if (it == q->qpp.end()) {
+  DevMem* m = nullptr;
+  int     r = q->qpp.get(K, &m, [&](DevMem& d) -> int {
     const int ki = lte_cb_index_eq(K);
     if (ki < 0) return MI355_ERROR_INVALID_INPUTS;
     const uint64_t        f1 = lte_qpp_table[ki][1], f2 = lte_qpp_table[ki][2];
     std::vector<uint16_t> t(K);
     for (uint64_t i = 0; i < K; i++) t[i] = (uint16_t)((f1 * i + f2 * i % K * i) % K);
-    uint16_t* d = nullptr;
-    CHECK_HIP(hipMalloc(&d, K * 2)); // hipMalloc alignment >= 256 B: the kernel reads 8 entries per 16-byte load
-    CHECK_HIP(hipMemcpy(d, t.data(), K * 2, hipMemcpyHostToDevice));
-    it = q->qpp.emplace(K, d).first;
-  }
-  *out = it->second;
-  return MI355_SUCCESS;
+    CHECK_HIP(d.upload(t)); // hipMalloc alignment >= 256 B: the kernel reads 8 entries per 16-byte load
+    return MI355_SUCCESS;
+  });
+  if (!r) *out = m->as<uint16_t>();
+  return r;
 }
 
-static int get_map(mi355_enb_dl_t* q, const mi355_pdsch_grant_t& g, uint32_t cfi, uint32_t sf, MapRef* out)
+static int get_map(mi355_enb_dl_t* q, const mi355_pdsch_grant_t& g, uint32_t cfi, uint32_t sf, MapRef** out)
 {
   std::string    key;
   const uint32_t hdr[4] = {cfi, sf, g.nof_symb_slot[0], g.nof_symb_slot[1]};
   key.append((const char*)hdr, sizeof(hdr));
   key.append((const char*)g.prb_idx[0], q->cell.nof_prb);
   key.append((const char*)g.prb_idx[1], q->cell.nof_prb);
-  auto it = q->maps.find(key);
-  if (it == q->maps.end()) {
-    if (q->maps.size() >= 4096) {
+  return q->maps.get(key, out, [&](MapRef& r) -> int {
+    if (q->maps.size() >= 4096) { // on a miss only; the new entry is inserted after the build
       CHECK_HIP(hipDeviceSynchronize());
-      for (auto& kv : q->maps) (void)hipFree(kv.second.d);
       q->maps.clear();
     }
     const uint32_t        n = mi355_pdsch_re_map(&q->cell, &g, cfi, sf, nullptr);
     std::vector<uint32_t> idx(n);
     mi355_pdsch_re_map(&q->cell, &g, cfi, sf, idx.data());
     std::vector<uint16_t> m(idx.begin(), idx.end());
-    MapRef                r;
     r.n = n;
-    CHECK_HIP(hipMalloc(&r.d, std::max<size_t>(n, 1) * 2));
-    if (n) CHECK_HIP(hipMemcpy(r.d, m.data(), n * 2, hipMemcpyHostToDevice));
-    it = q->maps.emplace(key, r).first;
-  }
-  *out = it->second;
-  return MI355_SUCCESS;
+    CHECK_HIP(r.d.upload(m));
+    return MI355_SUCCESS;
+  });
 }
 
 extern "C" {
@@ -205,17 +177,12 @@ int mi355_enb_dl_create(mi355_enb_dl_t** q, const mi355_cell_t* cell, int device
   const std::vector<float2>   pil = crs_table(*cell);
   const CrcTable              t[2] = {make_crc_table(0x1864CFB), make_crc_table(0x1800063)};
   if (hipStreamCreateWithFlags(&d->own, hipStreamNonBlocking) != hipSuccess ||
-      hipMalloc(&d->crc, sizeof(t)) != hipSuccess || hipMemcpy(d->crc, t, sizeof(t), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMalloc(&d->gold, g.size() * 4) != hipSuccess ||
-      hipMemcpy(d->gold, g.data(), g.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMalloc(&d->pilots, pil.size() * sizeof(float2)) != hipSuccess ||
-      hipMemcpy(d->pilots, pil.data(), pil.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMalloc(&d->tw, N * sizeof(float2)) != hipSuccess ||
-      hipMemcpy(d->tw, tw.data(), N * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess) {
+      d->crc.upload(t, sizeof(t)) != hipSuccess || d->gold.upload(g) != hipSuccess ||
+      d->pilots.upload(pil) != hipSuccess || d->tw.upload(tw) != hipSuccess) {
     mi355_enb_dl_destroy(d);
     return MI355_ERROR;
   }
-  a.tw = d->tw;
+  a.tw = d->tw.as<float2>();
   *q   = d;
   return MI355_SUCCESS;
 }
@@ -225,15 +192,6 @@ void mi355_enb_dl_destroy(mi355_enb_dl_t* q)
   if (!q) return;
   (void)hipSetDevice(q->device);
   (void)hipDeviceSynchronize();
-  for (auto& kv : q->scr) (void)hipFree(kv.second);
-  for (auto& kv : q->txt) (void)hipFree(kv.second);
-  for (auto& kv : q->qpp) (void)hipFree(kv.second);
-  for (auto& kv : q->maps) (void)hipFree(kv.second.d);
-  if (q->crc) (void)hipFree(q->crc);
-  if (q->gold) (void)hipFree(q->gold);
-  if (q->pilots) (void)hipFree(q->pilots);
-  if (q->tw) (void)hipFree(q->tw);
-  if (q->scratch) (void)hipFree(q->scratch);
   if (q->own) (void)hipStreamDestroy(q->own);
   delete q;
 }
@@ -259,7 +217,6 @@ int mi355_enb_dl_put_pdsch_batch(mi355_enb_dl_t* q, const mi355_enb_dl_pdsch_job
   const float               n16 = 1.0f / sqrtf(10.0f), n64 = 1.0f / sqrtf(42.0f), n256 = 1.0f / sqrtf(170.0f);
   if (q->scr.size() > 4096) {
     CHECK_HIP(hipStreamSynchronize(s));
-    for (auto& kv : q->scr) (void)hipFree(kv.second);
     q->scr.clear();
   }
   struct CwPlan {
@@ -272,13 +229,13 @@ int mi355_enb_dl_put_pdsch_batch(mi355_enb_dl_t* q, const mi355_enb_dl_pdsch_job
     const mi355_pdsch_grant_t&      g  = J.cfg.grant;
     const uint32_t                  sf = J.sf.tti % 10;
     if (g.nof_tb == 0 || g.nof_tb > 2) return MI355_ERROR_INVALID_INPUTS;
-    MapRef mr;
+    MapRef* mr = nullptr;
     if (get_map(q, g, J.sf.cfi, sf, &mr)) return MI355_ERROR;
-    const uint32_t nre = mr.n;
+    const uint32_t nre = mr->n;
     if (nre != g.nof_re || nre == 0) return MI355_ERROR_INVALID_INPUTS;
     EnbMapDev& M = maps[i];
     M            = EnbMapDev{};
-    M.map        = mr.d;
+    M.map        = mr->d.as<uint16_t>();
     M.nre        = nre;
     M.nports     = cell.nof_ports;
     M.nlayers    = g.nof_layers;
@@ -306,15 +263,14 @@ int mi355_enb_dl_put_pdsch_batch(mi355_enb_dl_t* q, const mi355_enb_dl_pdsch_job
       M.qm[cw]          = qm;
       // scrambling sequence (pdsch.c:1189-1195 c_init)
       const uint32_t c_init = ((uint32_t)J.cfg.rnti << 14) + (cw << 13) + (sf << 9) + cell.id;
-      auto           it     = q->scr.find(c_init);
-      if (it == q->scr.end()) {
-        uint32_t* dsc = nullptr;
-        CHECK_HIP(hipMalloc(&dsc, (PDSCH_GOLD_MAX / 32) * 4));
-        it = q->scr.emplace(c_init, dsc).first;
+      void*          dsc    = nullptr;
+      bool           fresh  = false; // filled by the scrambling-pack kernel below
+      CHECK_HIP(q->scr.get_alloc(c_init, (PDSCH_GOLD_MAX / 32) * 4, &dsc, &fresh));
+      if (fresh) {
         new_ci.push_back(c_init);
-        new_dst.push_back(dsc);
+        new_dst.push_back((uint32_t*)dsc);
       }
-      M.scr[cw]      = it->second;
+      M.scr[cw]      = (const uint32_t*)dsc;
       CwPlan& P      = cwp[2 * (size_t)i + cw];
       P.e_off        = ebits;
       ebits += (tb.nof_bits + 255) / 256 * 256;
@@ -406,9 +362,9 @@ int mi355_enb_dl_put_pdsch_batch(mi355_enb_dl_t* q, const mi355_enb_dl_pdsch_job
   const size_t o_ds = q->st.put(new_dst.data(), nci * 8);
   if (upload_on(q->st, base, s)) return MI355_ERROR;
   if (nci) CHECK_HIP(pdsch_launch_scr_pack((const uint32_t*)(base + o_ci), (uint32_t* const*)(base + o_ds), (uint32_t)nci,
-                                           q->gold, PDSCH_GOLD_MAX / 32, s));
-  CHECK_HIP(enb_launch_tb_crc((const EnbTbDev*)(base + o_tb), (uint32_t)ntb, q->crc, s));
-  CHECK_HIP(enb_launch_cb_encode((const EnbCbDev*)(base + o_cb), (uint32_t)ncb, q->crc + 1, s));
+                                           q->gold.as<uint32_t>(), PDSCH_GOLD_MAX / 32, s));
+  CHECK_HIP(enb_launch_tb_crc((const EnbTbDev*)(base + o_tb), (uint32_t)ntb, q->crc.as<CrcTable>(), s));
+  CHECK_HIP(enb_launch_cb_encode((const EnbCbDev*)(base + o_cb), (uint32_t)ncb, q->crc.as<CrcTable>() + 1, s));
   CHECK_HIP(enb_launch_map((const EnbMapDev*)(base + o_mp), njobs, max_units, s));
   if (!stream) CHECK_HIP(hipStreamSynchronize(s));
   return MI355_SUCCESS;
@@ -436,7 +392,8 @@ int mi355_enb_dl_put_refs_batch(mi355_enb_dl_t* q, const uint32_t* tti, float* c
   if (q->st.reserve(nsf * sizeof(EnbCrsJob)) != hipSuccess) return MI355_ERROR;
   q->st.put(jobs.data(), nsf * sizeof(EnbCrsJob));
   if (upload_on(q->st, base, s)) return MI355_ERROR;
-  CHECK_HIP(enb_launch_crs((const EnbCrsJob*)base, nsf, q->pilots, q->cell.nof_prb, np, q->cell.id, q->ofdm.nsymb, s));
+  CHECK_HIP(enb_launch_crs((const EnbCrsJob*)base, nsf, q->pilots.as<float2>(), q->cell.nof_prb, np, q->cell.id,
+                           q->ofdm.nsymb, s));
   if (!stream) CHECK_HIP(hipStreamSynchronize(s));
   return MI355_SUCCESS;
 }

@@ -12,20 +12,12 @@
 #include <string.h>
 #include <vector>
 
+#include "device_mem.h"
 #include "host_staging.h"
 #include "lte_common.h"
 #include "pdcch_internal.h"
 #include "host_parallel.h"
 #include "pdcch_runtime.h"
-
-#define CHECK_HIP(x)                                                                                                   \
-  do {                                                                                                                 \
-    hipError_t e_ = (x);                                                                                               \
-    if (e_ != hipSuccess) {                                                                                            \
-      fprintf(stderr, "[srsran_amd] %s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_));                 \
-      return MI355_ERROR;                                                                                              \
-    }                                                                                                                  \
-  } while (0)
 
 namespace mi355 {
 
@@ -34,8 +26,6 @@ CtrlState::~CtrlState()
   for (hipEvent_t e : ev) (void)hipEventDestroy(e);
   for (hipEvent_t e : kev) (void)hipEventDestroy(e);
   if (rb) (void)hipStreamDestroy(rb);
-  (void)hipFree(d_tab);
-  (void)hipFree(d_buf);
   delete st;
   delete back;
 }
@@ -61,8 +51,7 @@ int CtrlState::init(const mi355_cell_t& c, uint32_t nrx)
     for (uint32_t j = 0; j < 32 * seq_words; j++)
       tab[16 + 3 * PDCCH_MAX_REGS * 4 + 10 + sf * seq_words + j / 32] |= (uint32_t)c0[j] << (j % 32);
   }
-  CHECK_HIP(hipMalloc(&d_tab, tab.size() * 4));
-  CHECK_HIP(hipMemcpy(d_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice));
+  CHECK_HIP(d_tab.upload(tab));
   st   = new HostStaging;
   back = new HostStaging;
   return MI355_SUCCESS;
@@ -90,16 +79,8 @@ int CtrlState::launch(const mi355_dl_sf_job_t* sfjobs, const float* host_noise, 
   const size_t   b_cand = staged_size((size_t)n * PDCCH_SLOTS * PDCCH_FMTS * sizeof(DciCand));
   const size_t   b_hits = staged_size((size_t)n * sizeof(DciHits));
   const size_t   need   = b_jobs + b_blind + b_llr + b_cfi + b_corr + b_cand + b_hits;
-  if (need > cap) {
-    if (d_buf) {
-      CHECK_HIP(hipStreamSynchronize(s));
-      CHECK_HIP(hipFree(d_buf));
-      d_buf = nullptr;
-    }
-    cap = need + need / 4;
-    CHECK_HIP(hipMalloc(&d_buf, cap));
-  }
-  char* base = d_buf;
+  CHECK_HIP(d_buf.reserve(need, need + need / 4, DevScratch::SyncFree));
+  char* base = d_buf.base();
   plan_of.resize(n);
   CHECK_HIP(st->reserve(b_jobs + b_blind));
   auto* cj = (CtrlJob*)st->slot((size_t)n * sizeof(CtrlJob));
@@ -169,9 +150,9 @@ int CtrlState::launch(const mi355_dl_sf_job_t* sfjobs, const float* host_noise, 
     CtrlArgs a{};
     a.jobs       = inl ? nullptr : (const CtrlJob*)base + o;
     if (inl) a.inl = cj[0];
-    a.pcfich_re  = d_tab;
-    a.pdcch_re   = d_tab + 16;
-    a.pcfich_seq = d_tab + 16 + 3 * PDCCH_MAX_REGS * 4;
+    a.pcfich_re  = d_tab.as<uint32_t>();
+    a.pdcch_re   = a.pcfich_re + 16;
+    a.pcfich_seq = a.pcfich_re + 16 + 3 * PDCCH_MAX_REGS * 4;
     a.pdcch_seq  = a.pcfich_seq + 10;
     a.seq_words  = seq_words;
     for (int k = 0; k < 3; k++) a.nregs[k] = regs.nregs[k];

@@ -6,6 +6,7 @@
 #include <unordered_map>
 #include <vector>
 
+#include "device_mem.h"
 #include "pdcch_internal.h"
 
 namespace mi355 {
@@ -16,10 +17,9 @@ struct CtrlState {
   mi355_cell_t cell{};
   uint32_t     nof_rx    = 1;
   RegMap       regs;
-  uint32_t*    d_tab     = nullptr; // REG map + scrambling words, resident
+  DevMem       d_tab;               // REG map + scrambling words (uint32_t), resident
   uint32_t     seq_words = 0;
-  char*        d_buf     = nullptr; // per-call arena: descriptors | LLRs | CFIs | correlations | candidates
-  size_t       cap       = 0;
+  DevScratch   d_buf;               // per-call arena: descriptors | LLRs | CFIs | correlations | candidates
   HostStaging* st        = nullptr;
   HostStaging* back      = nullptr;
   uint32_t     last_n = 0, last_stride = 0; // the previous call's arena layout (inspection accessors)

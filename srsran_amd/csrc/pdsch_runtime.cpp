@@ -24,6 +24,7 @@
 #include "../../include/srsran_amd/dlsch.h"
 #include "../../include/srsran_amd/pdsch.h"
 #include "../../include/srsran_amd/tdec.h"
+#include "device_mem.h"
 #include "host_staging.h"
 #include "lte_common.h"
 #include "pdsch_internal.h"
@@ -31,15 +32,6 @@
 #include "runtime_internal.h"
 
 using namespace mi355;
-
-#define CHECK_HIP(x)                                                                                                   \
-  do {                                                                                                                 \
-    hipError_t e_ = (x);                                                                                               \
-    if (e_ != hipSuccess) {                                                                                            \
-      fprintf(stderr, "[srsran_amd] %s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_));                 \
-      return MI355_ERROR;                                                                                              \
-    }                                                                                                                  \
-  } while (0)
 
 namespace {
 std::atomic<unsigned long long*> g_eqrm_prof{nullptr};
@@ -160,10 +152,13 @@ uint32_t mod_bits(uint32_t mod)
 // g0 + t -> RE index or 0xffff (g1 - g0)], the inverse letting the single-RE equalisers walk the grid
 struct MapEntry {
   uint16_t* d = nullptr;
-  size_t    bytes = 0; // capacity of d
   uint32_t  n = 0, g0 = 0, g1 = 0, ncols = 0;
   const uint16_t* inv() const { return d + ((n + 1) & ~1u); }
   const uint16_t* cols() const { return inv() + (g1 - g0); } // distinct subcarriers of the REs
+};
+// the cache's entry: the map and the buffer d points into (recycled through map_free, trim_maps)
+struct MapSlot : MapEntry {
+  DevMem mem;
 };
 
 struct JobPlan {
@@ -191,21 +186,19 @@ struct mi355_pdsch {
   hipStream_t                          own    = nullptr;
   mi355_dlsch_t*                       dlsch  = nullptr;
   uint32_t                             max_its = 10; // SRSLTE_PDSCH_MAX_TDEC_ITERS
-  uint32_t*                            gold   = nullptr;
-  std::map<std::string, MapEntry>      maps; // extraction maps in HBM
+  DevMem                               gold; // uint32_t
+  DevCache<std::string, MapSlot>       maps; // extraction maps in HBM
   // the previous lookup per subframe index (key below): a batch of consecutive subframes cycles through them
   MapEntry                             last_map[10]{};
   uint32_t                             last_map_hdr[10][4]{};
   uint8_t                              last_map_prb[10][2][MI355_MAX_PRB]{};
-  std::unordered_map<uint32_t, uint32_t*> scr; // packed descrambling sequences per c_init (HBM)
+  DevCache<uint32_t, DevMem, std::unordered_map<uint32_t, DevMem>> scr; // packed descrambling sequences per c_init
   // bounds of the two caches, checked once per call before planning (mi355_pdsch_debug_set_cache_limits)
   uint32_t                             max_maps = 8192, max_scr = 4096;
-  char*                                scratch = nullptr;
-  size_t                               scratch_cap = 0;
-  // outgrown scratch buffers and evicted extraction maps: freed at destroy (hipFree waits for the whole device, which
-  // would stall every other worker's stream), the maps' buffers reused for new maps
-  std::vector<void*>                   retired;
-  std::vector<std::pair<void*, size_t>> map_free; // (buffer, bytes)
+  DevScratch                           scratch;
+  // evicted extraction maps' buffers: freed at destroy (hipFree waits for the whole device, which would stall every
+  // other worker's stream) and reused for new maps
+  std::vector<DevMem>                  map_free;
   std::vector<JobPlan>                 last; // plans of the last call (debug_stage)
   float2*                              d_arena   = nullptr;
   float*                               csi_arena = nullptr;
@@ -226,15 +219,9 @@ struct mi355_pdsch {
 
 static int get_scratch(mi355_pdsch_t* q, size_t bytes, char** p)
 {
-  if (bytes > q->scratch_cap) {
-    // the old scratch may still be read by this object's batch in flight: retired, not freed (no device-wide wait)
-    if (q->scratch) q->retired.push_back(q->scratch);
-    q->scratch = nullptr;
-    const size_t cap = bytes + bytes / 4 + 4096;
-    CHECK_HIP(hipMalloc(&q->scratch, cap));
-    q->scratch_cap = cap;
-  }
-  *p = q->scratch;
+  // the old scratch may still be read by this object's batch in flight: retired, not freed (no device-wide wait)
+  CHECK_HIP(q->scratch.reserve(bytes, bytes + bytes / 4 + 4096, DevScratch::Retire));
+  *p = q->scratch.base();
   return MI355_SUCCESS;
 }
 
@@ -247,7 +234,7 @@ static int trim_maps(mi355_pdsch_t* q)
 {
   if (q->maps.size() < q->max_maps) return MI355_SUCCESS;
   if (q->fe_armed) CHECK_HIP(wait_event(q->fe_done));
-  for (auto& kv : q->maps) q->map_free.emplace_back(kv.second.d, kv.second.bytes);
+  for (auto& kv : q->maps.map) q->map_free.push_back(std::move(kv.second.mem));
   q->maps.clear();
   for (auto& m : q->last_map) m = MapEntry{};
   return MI355_SUCCESS;
@@ -269,12 +256,11 @@ static int get_map(mi355_pdsch_t* q, const mi355_pdsch_grant_t& g, uint32_t cfi,
   key.append((const char*)hdr, sizeof(hdr));
   key.append((const char*)g.prb_idx[0], q->cell.nof_prb);
   key.append((const char*)g.prb_idx[1], q->cell.nof_prb);
-  auto it = q->maps.find(key);
-  if (it == q->maps.end()) {
+  MapSlot* slot = nullptr;
+  int      r    = q->maps.get(key, &slot, [&](MapSlot& e) -> int {
     std::vector<uint16_t> idx;
     idx.reserve(14 * 12 * q->cell.nof_prb);
     walk_map(q->cell, g, cfi, sf, [&](uint32_t, uint32_t p) { idx.push_back((uint16_t)p); });
-    MapEntry e;
     e.n = (uint32_t)idx.size();
     if (e.n) {
       e.g0 = *std::min_element(idx.begin(), idx.end());
@@ -292,29 +278,21 @@ static int get_map(mi355_pdsch_t* q, const mi355_pdsch_grant_t& g, uint32_t cfi,
     for (uint32_t i = 0; i < e.n; i++) all[((e.n + 1) & ~1u) + idx[i] - e.g0] = (uint16_t)i;
     std::copy(cols.begin(), cols.end(), all.begin() + ((e.n + 1) & ~1u) + (e.g1 - e.g0));
     const size_t need = std::max<size_t>(all.size(), 1) * sizeof(uint16_t);
-    e.d               = nullptr;
     for (size_t k = 0; k < q->map_free.size(); k++) // an evicted map's buffer that fits
-      if (q->map_free[k].second >= need) {
-        e.d     = (uint16_t*)q->map_free[k].first;
-        e.bytes = q->map_free[k].second;
-        q->map_free[k] = q->map_free.back();
+      if (q->map_free[k].bytes >= need) {
+        std::swap(e.mem, q->map_free[k]);
+        std::swap(q->map_free[k], q->map_free.back());
         q->map_free.pop_back();
         break;
       }
-    if (!e.d) {
-      CHECK_HIP(hipMalloc(&e.d, need));
-      e.bytes = need;
-    }
-    if (!all.empty()) {
-      CHECK_HIP(hipMemcpy(e.d, all.data(), all.size() * 2, hipMemcpyHostToDevice));
-      // (a pageable-source copy may return before its DMA lands; the kernels that read the map run on non-blocking
-      // streams the null stream does not order against)
-      CHECK_HIP(hipStreamSynchronize(nullptr));
-    }
-    it = q->maps.emplace(key, e).first;
-  }
-  *out           = it->second;
-  q->last_map[z] = it->second;
+    if (!e.mem.p) CHECK_HIP(e.mem.alloc(need));
+    CHECK_HIP(e.mem.upload(all)); // into the buffer just chosen (waits for the copy to land, device_mem.h)
+    e.d = e.mem.as<uint16_t>();
+    return MI355_SUCCESS;
+  });
+  if (r) return r;
+  *out           = *slot;
+  q->last_map[z] = *slot;
   const uint32_t h[4] = {cfi, sf, g.nof_symb_slot[0], g.nof_symb_slot[1]};
   memcpy(q->last_map_hdr[z], h, sizeof(h));
   memcpy(q->last_map_prb[z][0], g.prb_idx[0], np);
@@ -430,7 +408,6 @@ static int run_frontend(mi355_pdsch_t* q, const mi355_pdsch_job_t* jobs, std::ve
   std::vector<uint32_t*>  new_dst;
   if (q->scr.size() > q->max_scr) { // bound the sequence cache (~76 MB at 4096)
     CHECK_HIP(hipStreamSynchronize(s));
-    for (auto& kv : q->scr) (void)hipFree(kv.second);
     q->scr.clear();
   }
   uint32_t  max_units = 0, max_pairs = 0, max_fpairs = 0;
@@ -465,15 +442,14 @@ static int run_frontend(mi355_pdsch_t* q, const mi355_pdsch_job_t* jobs, std::ve
       if (c.c_init == last_ci && last_scr) {
         c.scr = last_scr;
       } else {
-        auto it = q->scr.find(c.c_init);
-        if (it == q->scr.end()) {
-          uint32_t* d = nullptr;
-          CHECK_HIP(hipMalloc(&d, (PDSCH_GOLD_MAX / 32) * 4));
-          it = q->scr.emplace(c.c_init, d).first;
+        void* d     = nullptr;
+        bool  fresh = false; // filled by pdsch_launch_scr_pack below
+        CHECK_HIP(q->scr.get_alloc(c.c_init, (PDSCH_GOLD_MAX / 32) * 4, &d, &fresh));
+        if (fresh) {
           new_ci.push_back(c.c_init);
-          new_dst.push_back(d);
+          new_dst.push_back((uint32_t*)d);
         }
-        c.scr   = it->second;
+        c.scr   = (const uint32_t*)d;
         last_ci = c.c_init;
         last_scr = c.scr;
       }
@@ -580,7 +556,7 @@ static int run_frontend(mi355_pdsch_t* q, const mi355_pdsch_job_t* jobs, std::ve
   CHECK_HIP(pdsch_launch_equalize((const PdschJobDev*)(base + o_jobs), njobs, max_units, s));
   const auto tl0 = now();
   CHECK_HIP(pdsch_launch_scr_pack((const uint32_t*)(base + o_nci), (uint32_t* const*)(base + o_ndst),
-                                  (uint32_t)new_ci.size(), q->gold, PDSCH_GOLD_MAX / 32, s));
+                                  (uint32_t)new_ci.size(), q->gold.as<uint32_t>(), PDSCH_GOLD_MAX / 32, s));
   const auto tl1 = now();
   q->e_pending = er != nullptr;
   if (er) {
@@ -632,8 +608,7 @@ int mi355_pdsch_create(mi355_pdsch_t** q, const mi355_cell_t* cell, uint32_t nof
   const std::vector<uint32_t> g = gold_table(PDSCH_GOLD_MAX);
   if (hipStreamCreateWithFlags(&d->own, hipStreamNonBlocking) != hipSuccess ||
       mi355_dlsch_create(&d->dlsch, device) != MI355_SUCCESS ||
-      hipMalloc(&d->gold, g.size() * 4) != hipSuccess ||
-      hipMemcpy(d->gold, g.data(), g.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+      d->gold.upload(g) != hipSuccess) {
     mi355_pdsch_destroy(d);
     return MI355_ERROR;
   }
@@ -646,12 +621,6 @@ void mi355_pdsch_destroy(mi355_pdsch_t* q)
   if (!q) return;
   (void)hipSetDevice(q->device);
   (void)hipDeviceSynchronize();
-  for (auto& kv : q->maps) (void)hipFree(kv.second.d);
-  for (auto& f : q->map_free) (void)hipFree(f.first);
-  for (void* r : q->retired) (void)hipFree(r);
-  for (auto& kv : q->scr) (void)hipFree(kv.second);
-  (void)hipFree(q->gold);
-  (void)hipFree(q->scratch);
   if (q->fe_done) (void)hipEventDestroy(q->fe_done);
   mi355_dlsch_destroy(q->dlsch);
   if (q->own) (void)hipStreamDestroy(q->own);

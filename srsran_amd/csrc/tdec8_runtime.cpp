@@ -10,36 +10,27 @@
 #include <vector>
 
 #include "../../include/srsran_amd/tdec.h"
+#include "device_mem.h"
 #include "lte_qpp_table.h"
 #include "rm_tables.h"
 #include "tdec8_internal.h"
 
 using namespace mi355;
 
-#define CHECK_HIP(x)                                                                                                   \
-  do {                                                                                                                 \
-    hipError_t e_ = (x);                                                                                               \
-    if (e_ != hipSuccess) {                                                                                            \
-      fprintf(stderr, "[srsran_amd] %s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_));                 \
-      return MI355_ERROR;                                                                                              \
-    }                                                                                                                  \
-  } while (0)
-
 struct mi355_tdec8 {
   int                                 device = 0;
   hipStream_t                         own    = nullptr;
-  int8_t*                             ws     = nullptr;
-  size_t                              ws_cap = 0;
-  std::map<uint32_t, uint16_t*>       interl; // K -> [forward K | reverse K], window-ordered (NB of K)
-  std::map<uint64_t, uint16_t*>       rm_inv; // (K << 2 | rv) -> inverse deinterleaver
+  DevScratch                          ws;
+  DevCache<uint32_t>                  interl; // K -> [forward K | reverse K], window-ordered (NB of K)
+  DevCache<uint64_t>                  rm_inv; // (K << 2 | rv) -> inverse deinterleaver
   std::mutex                          mu;
 };
 
 // srslte_tc_interl_LTE_gen_interl with interl_win = NB (tc_interl_lte.c:69-107)
 static int get_interl(mi355_tdec8_t* q, uint32_t K, uint32_t NB, const uint16_t** out)
 {
-  auto it = q->interl.find(K);
-  if (it == q->interl.end()) {
+  DevMem* m = nullptr;
+  int     e = q->interl.get(K, &m, [&](DevMem& d) -> int {
     const int idx = lte_cb_index_eq(K);
     if (idx < 0) return MI355_ERROR_INVALID_INPUTS;
     const uint64_t        f1 = lte_qpp_table[idx][1], f2 = lte_qpp_table[idx][2];
@@ -56,13 +47,11 @@ static int get_interl(mi355_tdec8_t* q, uint32_t K, uint32_t NB, const uint16_t*
       t[i]     = (uint16_t)deinter(f[inter(i)]);
       t[K + i] = (uint16_t)deinter(r[inter(i)]);
     }
-    uint16_t* d = nullptr;
-    CHECK_HIP(hipMalloc(&d, t.size() * 2));
-    CHECK_HIP(hipMemcpy(d, t.data(), t.size() * 2, hipMemcpyHostToDevice));
-    it = q->interl.emplace(K, d).first;
-  }
-  *out = it->second;
-  return MI355_SUCCESS;
+    CHECK_HIP(d.upload(t));
+    return MI355_SUCCESS;
+  });
+  if (!e) *out = m->as<uint16_t>();
+  return e;
 }
 
 // one half-iteration n over the batch b (K, in, slot/done/running set by the caller); the caller holds q->mu or
@@ -76,17 +65,11 @@ int mi355::tdec8_halfit_batch(mi355_tdec8_t* q, T8Batch b, uint32_t n, uint8_t* 
   if (r) return r;
   const uint32_t L         = K / NB;
   const size_t   ws_stride = (4 * (size_t)(K + 32) + 8 * (size_t)(L + 1) * NB + 255) / 256 * 256;
-  if (ws_stride * b.ncb > q->ws_cap) {
+  if (ws_stride * b.ncb > q->ws.cap()) {
     if (n) return MI355_ERROR_INVALID_INPUTS; // a later half-iteration of a batch that was never started
-    if (q->ws) {
-      CHECK_HIP(hipDeviceSynchronize());
-      CHECK_HIP(hipFree(q->ws));
-      q->ws = nullptr;
-    }
-    q->ws_cap = ws_stride * b.ncb;
-    CHECK_HIP(hipMalloc(&q->ws, q->ws_cap));
+    CHECK_HIP(q->ws.reserve(ws_stride * b.ncb, ws_stride * b.ncb, DevScratch::SyncFree));
   }
-  b.ws = q->ws, b.ws_stride = ws_stride, b.NB = NB, b.L = L;
+  b.ws = (int8_t*)q->ws.base(), b.ws_stride = ws_stride, b.NB = NB, b.L = L;
   Tdec8MapArgs a{};
   a.b = b;
   int src;
@@ -131,9 +114,6 @@ void mi355_tdec8_destroy(mi355_tdec8_t* q)
   if (!q) return;
   (void)hipSetDevice(q->device);
   (void)hipDeviceSynchronize();
-  for (auto& kv : q->interl) (void)hipFree(kv.second);
-  for (auto& kv : q->rm_inv) (void)hipFree(kv.second);
-  if (q->ws) (void)hipFree(q->ws);
   if (q->own) (void)hipStreamDestroy(q->own);
   delete q;
 }
@@ -187,17 +167,16 @@ int mi355_rm_turbo_rx_8bit_dev(mi355_tdec8_t* q, const int8_t* e, size_t e_strid
   CHECK_HIP(hipSetDevice(q->device));
   hipStream_t    s   = stream ? (hipStream_t)stream : q->own;
   const uint64_t key = ((uint64_t)K << 2) | rv;
-  auto           it  = q->rm_inv.find(key);
-  if (it == q->rm_inv.end()) {
+  DevMem*        m   = nullptr;
+  int            r   = q->rm_inv.get(key, &m, [&](DevMem& d) -> int {
     const std::vector<uint16_t> t = rm_rx_table_nsb(K, rv, nsb); // circular index -> decoder position
     std::vector<uint16_t>       inv(buflen, 0xffff);
     for (uint32_t i = 0; i < N; i++) inv[t[i]] = (uint16_t)i;
-    uint16_t* d = nullptr;
-    CHECK_HIP(hipMalloc(&d, inv.size() * 2));
-    CHECK_HIP(hipMemcpy(d, inv.data(), inv.size() * 2, hipMemcpyHostToDevice));
-    it = q->rm_inv.emplace(key, d).first;
-  }
-  Rm8Args a{e, e_stride, out, out_stride, it->second, N, E, buflen, ncb};
+    CHECK_HIP(d.upload(inv));
+    return MI355_SUCCESS;
+  });
+  if (r) return r;
+  Rm8Args a{e, e_stride, out, out_stride, m->as<uint16_t>(), N, E, buflen, ncb};
   CHECK_HIP(rm8_launch_rx(a, s));
   if (!stream) CHECK_HIP(hipStreamSynchronize(s));
   return MI355_SUCCESS;

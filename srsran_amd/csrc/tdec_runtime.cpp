@@ -13,19 +13,11 @@
 #include <vector>
 
 #include "../../include/srsran_amd/tdec.h"
+#include "device_mem.h"
 #include "lte_qpp_table.h"
 #include "tdec_internal.h"
 
 using namespace mi355;
-
-#define CHECK_HIP(x)                                                                                                   \
-  do {                                                                                                                 \
-    hipError_t e_ = (x);                                                                                               \
-    if (e_ != hipSuccess) {                                                                                            \
-      fprintf(stderr, "[srsran_amd] %s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_));                 \
-      return MI355_ERROR;                                                                                              \
-    }                                                                                                                  \
-  } while (0)
 
 namespace {
 
@@ -41,9 +33,8 @@ int cb_index(uint32_t K)
 uint32_t round_up(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
 
 struct KTables {
-  uint32_t* dstE = nullptr; // window mode
-  uint32_t* dstA = nullptr;
-  uint16_t* pi   = nullptr; // generic mode
+  DevMem dstE, dstA; // window mode (uint32_t)
+  DevMem pi;         // generic mode (uint16_t)
 };
 
 struct Geometry {
@@ -75,14 +66,13 @@ Geometry geometry(uint32_t K, uint32_t ncb, int impl)
 struct mi355_tdec_batch {
   int                          device = 0;
   hipStream_t                  own    = nullptr;
-  char*                        ws     = nullptr;
-  size_t                       ws_cap = 0;
-  std::map<uint32_t, KTables>  tables;     // window-mode tables per K
-  std::map<uint32_t, KTables>  gtables;    // generic-mode tables per K
+  DevScratch                   ws;
+  DevCache<uint32_t, KTables>  tables;     // window-mode tables per K
+  DevCache<uint32_t, KTables>  gtables;    // generic-mode tables per K
   int                          impl = MI355_TDEC_AUTO;
   int                          gen_cb   = -1; // generic decoder: per-code-block workgroups (1), pair lanes (0), auto (-1)
   int                          gen_warm = 32; // its guessed-state warm-up (rows / steps)
-  uint32_t*                    reruns   = nullptr; // device counter of its chunk reruns
+  DevMem                       reruns;            // device counter (uint32_t) of its chunk reruns
   bool                         prof = false;
   std::vector<hipEvent_t>      ev;
   size_t                       ev_used = 0;
@@ -91,49 +81,39 @@ struct mi355_tdec_batch {
 
 static int get_tables(mi355_tdec_batch_t* q, const Geometry& g, KTables** out)
 {
-  auto& cache = g.nsb ? q->tables : q->gtables;
-  auto  it    = cache.find(g.K);
-  if (it != cache.end()) {
-    *out = &it->second;
-    return MI355_SUCCESS;
-  }
-  const uint32_t K   = g.K;
-  const int      idx = cb_index(K);
-  if (idx < 0) return MI355_ERROR_INVALID_INPUTS;
-  const uint64_t        f1 = lte_qpp_table[idx][1], f2 = lte_qpp_table[idx][2];
-  std::vector<uint16_t> pi(K), inv(K);
-  for (uint64_t m = 0; m < K; m++) {
-    pi[m]       = (uint16_t)((f1 * m + f2 * m * m) % K);
-    inv[pi[m]]  = (uint16_t)m;
-  }
-  KTables t;
-  if (g.nsb) {
-    // per (step j, lane l): destination row j' (shared by every window, QPP contention-freeness)
-    // and the destination windows of this lane's two windows
-    std::vector<uint32_t> dE((size_t)g.L * g.nl, 0), dA((size_t)g.L * g.nl, 0);
-    for (uint32_t j = 0; j < g.L; j++) {
-      for (uint32_t l = 0; l < g.nl; l++) {
-        uint32_t n0 = (2 * l) * g.L + j, n1 = (2 * l + 1) * g.L + j;
-        uint32_t e0 = inv[n0], e1 = inv[n1], a0 = pi[n0], a1 = pi[n1];
-        if (e0 % g.L != e1 % g.L || a0 % g.L != a1 % g.L) return MI355_ERROR; // not contention-free
-        // int16 offsets inside the wave group's row block: row j' (128 int16 per row) + window
-        dE[(size_t)j * g.nl + l] = ((e0 % g.L) * 128 + e0 / g.L) | (((e1 % g.L) * 128 + e1 / g.L) << 16);
-        dA[(size_t)j * g.nl + l] = ((a0 % g.L) * 128 + a0 / g.L) | (((a1 % g.L) * 128 + a1 / g.L) << 16);
-      }
+  return (g.nsb ? q->tables : q->gtables).get(g.K, out, [&](KTables& t) -> int {
+    const uint32_t K   = g.K;
+    const int      idx = cb_index(K);
+    if (idx < 0) return MI355_ERROR_INVALID_INPUTS;
+    const uint64_t        f1 = lte_qpp_table[idx][1], f2 = lte_qpp_table[idx][2];
+    std::vector<uint16_t> pi(K), inv(K);
+    for (uint64_t m = 0; m < K; m++) {
+      pi[m]       = (uint16_t)((f1 * m + f2 * m * m) % K);
+      inv[pi[m]]  = (uint16_t)m;
     }
-    CHECK_HIP(hipMalloc(&t.dstE, dE.size() * 4));
-    CHECK_HIP(hipMalloc(&t.dstA, dA.size() * 4));
-    CHECK_HIP(hipMemcpy(t.dstE, dE.data(), dE.size() * 4, hipMemcpyHostToDevice));
-    CHECK_HIP(hipMemcpy(t.dstA, dA.data(), dA.size() * 4, hipMemcpyHostToDevice));
-  } else {
-    std::vector<uint16_t> both(pi);
-    both.insert(both.end(), inv.begin(), inv.end());
-    CHECK_HIP(hipMalloc(&t.pi, 2 * K * 2));
-    CHECK_HIP(hipMemcpy(t.pi, both.data(), 2 * K * 2, hipMemcpyHostToDevice));
-  }
-  auto r = cache.emplace(K, t);
-  *out   = &r.first->second;
-  return MI355_SUCCESS;
+    if (g.nsb) {
+      // per (step j, lane l): destination row j' (shared by every window, QPP contention-freeness)
+      // and the destination windows of this lane's two windows
+      std::vector<uint32_t> dE((size_t)g.L * g.nl, 0), dA((size_t)g.L * g.nl, 0);
+      for (uint32_t j = 0; j < g.L; j++) {
+        for (uint32_t l = 0; l < g.nl; l++) {
+          uint32_t n0 = (2 * l) * g.L + j, n1 = (2 * l + 1) * g.L + j;
+          uint32_t e0 = inv[n0], e1 = inv[n1], a0 = pi[n0], a1 = pi[n1];
+          if (e0 % g.L != e1 % g.L || a0 % g.L != a1 % g.L) return MI355_ERROR; // not contention-free
+          // int16 offsets inside the wave group's row block: row j' (128 int16 per row) + window
+          dE[(size_t)j * g.nl + l] = ((e0 % g.L) * 128 + e0 / g.L) | (((e1 % g.L) * 128 + e1 / g.L) << 16);
+          dA[(size_t)j * g.nl + l] = ((a0 % g.L) * 128 + a0 / g.L) | (((a1 % g.L) * 128 + a1 / g.L) << 16);
+        }
+      }
+      CHECK_HIP(t.dstE.upload(dE));
+      CHECK_HIP(t.dstA.upload(dA));
+    } else {
+      std::vector<uint16_t> both(pi);
+      both.insert(both.end(), inv.begin(), inv.end());
+      CHECK_HIP(t.pi.upload(both));
+    }
+    return MI355_SUCCESS;
+  });
 }
 
 static size_t ws_bytes(const Geometry& g, uint32_t n, bool cbk = false)
@@ -150,15 +130,7 @@ static size_t ws_bytes(const Geometry& g, uint32_t n, bool cbk = false)
 
 static int ensure_ws(mi355_tdec_batch_t* q, size_t bytes)
 {
-  if (bytes <= q->ws_cap) return MI355_SUCCESS;
-  if (q->ws) {
-    CHECK_HIP(hipDeviceSynchronize());
-    CHECK_HIP(hipFree(q->ws));
-    q->ws = nullptr;
-  }
-  size_t cap = bytes + bytes / 8;
-  CHECK_HIP(hipMalloc(&q->ws, cap));
-  q->ws_cap = cap;
+  CHECK_HIP(q->ws.reserve(bytes, bytes + bytes / 8, DevScratch::SyncFree));
   return MI355_SUCCESS;
 }
 
@@ -203,16 +175,7 @@ void mi355_tdec_batch_destroy(mi355_tdec_batch_t* q)
   if (!q) return;
   (void)hipSetDevice(q->device);
   (void)hipDeviceSynchronize();
-  for (auto* m : {&q->tables, &q->gtables}) {
-    for (auto& kv : *m) {
-      (void)hipFree(kv.second.dstE);
-      (void)hipFree(kv.second.dstA);
-      (void)hipFree(kv.second.pi);
-    }
-  }
   for (auto e : q->ev) (void)hipEventDestroy(e);
-  if (q->ws) (void)hipFree(q->ws);
-  if (q->reruns) (void)hipFree(q->reruns);
   if (q->own) (void)hipStreamDestroy(q->own);
   delete q;
 }
@@ -251,8 +214,8 @@ int mi355_tdec_win_tables(mi355_tdec_batch_t* q, uint32_t K, const uint32_t** ds
   KTables*       t = nullptr;
   const int      r = get_tables(q, g, &t);
   if (r) return r;
-  *dstE = t->dstE;
-  *dstA = t->dstA;
+  *dstE = t->dstE.as<uint32_t>();
+  *dstA = t->dstA.as<uint32_t>();
   return MI355_SUCCESS;
 }
 
@@ -285,11 +248,11 @@ int mi355_tdec_run_internal(mi355_tdec_batch_t* q, const TdecRun& rq)
                    (q->gen_cb == 1 || (q->gen_cb < 0 && (K > 400 || n <= 4096)));
   if (h0 == 0) {
     if ((r = ensure_ws(q, ws_bytes(g, n, cbk)))) return r;
-  } else if (ws_bytes(g, n, cbk) > q->ws_cap) {
+  } else if (ws_bytes(g, n, cbk) > q->ws.cap()) {
     return MI355_ERROR; // continuation without a workspace holding the earlier half-iterations
   }
 
-  char* p     = q->ws;
+  char* p     = q->ws.base();
   auto  carve = [&](size_t bytes) {
     char* c = p;
     p += ((bytes + 255) / 256) * 256;
@@ -313,15 +276,16 @@ int mi355_tdec_run_internal(mi355_tdec_batch_t* q, const TdecRun& rq)
     // stores and the fused check's chunks)
     const bool fuse = (g.L % 8 == 0 || (K % 64 == 0 && (K / 8) % (g.nsb / 2) == 0)) && out_stride % 8 == 0 &&
                       (uintptr_t)d_out % 8 == 0;
+    const uint32_t *dstE = t->dstE.as<uint32_t>(), *dstA = t->dstA.as<uint32_t>();
     for (uint32_t h = h0; h < h1; h++) {
       if (rq.redo) { // again, the next half-iteration's input only, for the code blocks the check left unfinished
-        TdecWinArgs wa{d_in, in_stride, rq.in_idx, rq.done, rq.remaining, A1, E, D, CK, t->dstE, t->dstA,
+        TdecWinArgs wa{d_in, in_stride, rq.in_idx, rq.done, rq.remaining, A1, E, D, CK, dstE, dstA,
                        (int)n, (int)g.L, (int)g.Lp, (int)g.nseg, (int)h, 0, nullptr, out_stride};
         wa.rowmask = rq.rowmask && g.nsb == 16 && in_stride == SB_STRIDE;
         CHECK_HIP(tdec_win_launch_halfit(g.nsb, wa, s));
         continue;
       }
-      TdecWinArgs wa{d_in, in_stride, rq.in_idx, rq.done, rq.remaining, A1, E, D, CK, t->dstE, t->dstA,
+      TdecWinArgs wa{d_in, in_stride, rq.in_idx, rq.done, rq.remaining, A1, E, D, CK, dstE, dstA,
                      (int)n, (int)g.L, (int)g.Lp, (int)g.nseg, (int)h, h + 1 == h1,
                      (fuse && h + 1 == h1) ? d_out : nullptr, out_stride};
       wa.rowmask = rq.rowmask && g.nsb == 16 && in_stride == SB_STRIDE;
@@ -353,11 +317,11 @@ int mi355_tdec_run_internal(mi355_tdec_batch_t* q, const TdecRun& rq)
     ca.in         = d_in;
     ca.in_stride  = in_stride;
     ca.in_idx     = rq.in_idx;
-    ca.ws         = (uint16_t*)q->ws;
-    ca.pi         = t->pi;
+    ca.ws         = (uint16_t*)q->ws.base();
+    ca.pi         = t->pi.as<uint16_t>();
     ca.out        = d_out;
     ca.out_stride = out_stride;
-    ca.reruns     = q->reruns;
+    ca.reruns     = q->reruns.as<uint32_t>();
     ca.ncb        = (int)n;
     ca.K          = (int)K;
     ca.Kp         = TDEC_GEN_CB_KP((int)K);
@@ -388,7 +352,7 @@ int mi355_tdec_run_internal(mi355_tdec_batch_t* q, const TdecRun& rq)
       CHECK_HIP(tdec_gen_launch_prep(pa, s));
     }
     for (uint32_t h = h0; h < h1; h++) {
-      TdecGenArgs ga{S, P0, P1, A1, E, D, CK, t->pi,
+      TdecGenArgs ga{S, P0, P1, A1, E, D, CK, t->pi.as<uint16_t>(),
                      (int)g.npair, (int)K, (int)g.Kp, (int)g.nseg, (int)h, h + 1 == h1};
       hipEvent_t e0 = nullptr, e1 = nullptr;
       if (q->prof) {
@@ -450,15 +414,15 @@ int mi355_tdec_batch_generic_reruns(mi355_tdec_batch_t* q, uint32_t* reruns)
   if (!q || !reruns) return MI355_ERROR_INVALID_INPUTS;
   std::lock_guard<std::mutex> lock(q->mu);
   CHECK_HIP(hipSetDevice(q->device));
-  if (!q->reruns) {
-    CHECK_HIP(hipMalloc(&q->reruns, 4));
-    CHECK_HIP(hipMemset(q->reruns, 0, 4));
+  if (!q->reruns.p) {
+    CHECK_HIP(q->reruns.alloc(4));
+    CHECK_HIP(hipMemset(q->reruns.p, 0, 4));
     *reruns = 0;
     return MI355_SUCCESS;
   }
   CHECK_HIP(hipDeviceSynchronize());
-  CHECK_HIP(hipMemcpy(reruns, q->reruns, 4, hipMemcpyDeviceToHost));
-  CHECK_HIP(hipMemset(q->reruns, 0, 4));
+  CHECK_HIP(hipMemcpy(reruns, q->reruns.p, 4, hipMemcpyDeviceToHost));
+  CHECK_HIP(hipMemset(q->reruns.p, 0, 4));
   return MI355_SUCCESS;
 }
 
@@ -481,18 +445,16 @@ int mi355_tdec_batch_run(mi355_tdec_batch_t* q,
   if (!q || !in || !out) return MI355_ERROR_INVALID_INPUTS;
   if (n == 0) return MI355_SUCCESS;
   CHECK_HIP(hipSetDevice(q->device));
-  int16_t* din  = nullptr;
-  uint8_t* dout = nullptr;
-  CHECK_HIP(hipMalloc(&din, (size_t)n * in_stride * 2));
-  CHECK_HIP(hipMalloc(&dout, (size_t)n * out_stride));
-  CHECK_HIP(hipMemcpyAsync(din, in, (size_t)n * in_stride * 2, hipMemcpyHostToDevice, q->own));
-  int r = mi355_tdec_batch_run_dev(q, din, in_stride, n, K, nhalf, dout, out_stride, q->own);
+  DevMem din, dout; // freed on every return
+  CHECK_HIP(din.alloc((size_t)n * in_stride * 2));
+  CHECK_HIP(dout.alloc((size_t)n * out_stride));
+  CHECK_HIP(hipMemcpyAsync(din.p, in, (size_t)n * in_stride * 2, hipMemcpyHostToDevice, q->own));
+  int r = mi355_tdec_batch_run_dev(q, din.as<int16_t>(), in_stride, n, K, nhalf, dout.as<uint8_t>(), out_stride,
+                                   q->own);
   if (r == MI355_SUCCESS) {
-    CHECK_HIP(hipMemcpyAsync(out, dout, (size_t)n * out_stride, hipMemcpyDeviceToHost, q->own));
+    CHECK_HIP(hipMemcpyAsync(out, dout.p, (size_t)n * out_stride, hipMemcpyDeviceToHost, q->own));
     CHECK_HIP(hipStreamSynchronize(q->own));
   }
-  (void)hipFree(din);
-  (void)hipFree(dout);
   return r;
 }
 

@@ -17,6 +17,7 @@
 #include "../../include/srsran_amd/pdsch.h"
 #include "../../include/srsran_amd/tdec.h"
 #include "../../include/srsran_amd/ue_dl.h"
+#include "device_mem.h"
 #include "lte_common.h"
 #include "runtime_internal.h"
 #include "host_parallel.h"
@@ -26,15 +27,6 @@
 #include "wiener_bank.h"
 
 using namespace mi355;
-
-#define CHECK_HIP(x)                                                                                                   \
-  do {                                                                                                                 \
-    hipError_t e_ = (x);                                                                                               \
-    if (e_ != hipSuccess) {                                                                                            \
-      fprintf(stderr, "[srsran_amd] %s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_));                 \
-      return MI355_ERROR;                                                                                              \
-    }                                                                                                                  \
-  } while (0)
 
 namespace {
 
@@ -67,14 +59,11 @@ struct mi355_ue_dl {
   bool           std_rates = false;
   hipStream_t    own       = nullptr;
   OfdmArgs       ofdm{};
-  float2*        tw     = nullptr;
-  float2*        pilots = nullptr;
-  float2*        pss    = nullptr; // srslte_pss_generate(cell.id % 3)
+  DevMem         tw, pilots; // float2
+  DevMem         pss;        // float2: srslte_pss_generate(cell.id % 3)
   mi355_pdsch_t* pdsch  = nullptr;
   std::vector<ChestLink> links;
-  char*          scratch = nullptr;
-  size_t         scratch_cap = 0;
-  std::vector<void*> retired; // outgrown scratch, freed at destroy (hipFree waits for the whole device)
+  DevScratch     scratch;
   HostStaging    st_ofdm, st_chest, back; // pinned descriptor uploads / estimator read-back
   hipStream_t    side     = nullptr;       // estimator read-back + fill_res overlapping the PDSCH decode
   hipEvent_t     ev_chest = nullptr;
@@ -120,24 +109,17 @@ static int set_dft(mi355_ue_dl_t* q)
     const double ang = -2.0 * M_PI * (double)m / (double)N;
     tw[m]            = make_float2((float)std::cos(ang), (float)std::sin(ang));
   }
-  if (q->tw) CHECK_HIP(hipFree(q->tw));
-  CHECK_HIP(hipMalloc(&q->tw, N * sizeof(float2)));
-  CHECK_HIP(hipMemcpy(q->tw, tw.data(), N * sizeof(float2), hipMemcpyHostToDevice));
-  a.tw = q->tw;
+  q->tw.reset();
+  CHECK_HIP(q->tw.upload(tw));
+  a.tw = q->tw.as<float2>();
   return MI355_SUCCESS;
 }
 
 static int get_scratch(mi355_ue_dl_t* q, size_t bytes, char** p)
 {
-  if (bytes > q->scratch_cap) {
-    // may still be read by this object's batch in flight: retired, not freed (no device-wide wait)
-    if (q->scratch) q->retired.push_back(q->scratch);
-    q->scratch = nullptr;
-    const size_t cap = bytes + bytes / 4 + 4096;
-    CHECK_HIP(hipMalloc(&q->scratch, cap));
-    q->scratch_cap = cap;
-  }
-  *p = q->scratch;
+  // may still be read by this object's batch in flight: retired, not freed (no device-wide wait)
+  CHECK_HIP(q->scratch.reserve(bytes, bytes + bytes / 4 + 4096, DevScratch::Retire));
+  *p = q->scratch.base();
   return MI355_SUCCESS;
 }
 
@@ -391,8 +373,8 @@ static int chest_launch_only(mi355_ue_dl_t* q, const mi355_dl_sf_job_t* jobs, ui
     CHECK_HIP(q->st_chest.upload(base, s));
     ca.jobs = (const ChestJob*)base;
   }
-  ca.pilots      = q->pilots;
-  ca.pss         = q->pss;
+  ca.pilots      = q->pilots.as<float2>();
+  ca.pss         = q->pss.as<float2>();
   ca.out_all     = d_out;
   ca.nof_prb     = q->cell.nof_prb;
   ca.cell_id     = q->cell.id;
@@ -564,10 +546,7 @@ int mi355_ue_dl_create(mi355_ue_dl_t** q, const mi355_cell_t* cell, uint32_t nof
     }
   }
   if (hipStreamCreateWithFlags(&d->own, hipStreamNonBlocking) != hipSuccess || set_dft(d) != MI355_SUCCESS ||
-      hipMalloc(&d->pilots, pil.size() * sizeof(float2)) != hipSuccess ||
-      hipMemcpy(d->pilots, pil.data(), pil.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMalloc(&d->pss, pss.size() * sizeof(float2)) != hipSuccess ||
-      hipMemcpy(d->pss, pss.data(), pss.size() * sizeof(float2), hipMemcpyHostToDevice) != hipSuccess ||
+      d->pilots.upload(pil) != hipSuccess || d->pss.upload(pss) != hipSuccess ||
       mi355_pdsch_create(&d->pdsch, cell, nof_rx_antennas, device) != MI355_SUCCESS) {
     mi355_ue_dl_destroy(d);
     return MI355_ERROR;
@@ -581,11 +560,6 @@ void mi355_ue_dl_destroy(mi355_ue_dl_t* q)
   if (!q) return;
   (void)hipSetDevice(q->device);
   (void)hipDeviceSynchronize();
-  (void)hipFree(q->tw);
-  (void)hipFree(q->pilots);
-  (void)hipFree(q->pss);
-  (void)hipFree(q->scratch);
-  for (void* r : q->retired) (void)hipFree(r);
   mi355_pdsch_destroy(q->pdsch);
   if (q->own) (void)hipStreamDestroy(q->own);
   if (q->side) (void)hipStreamDestroy(q->side);
@@ -626,7 +600,7 @@ int mi355_ue_dl_reset_link(mi355_ue_dl_t* q, uint32_t link)
   if (!q || link >= MI355_MAX_LINKS) return MI355_ERROR_INVALID_INPUTS;
   std::lock_guard<std::mutex> lock(q->mu);
   if (link < q->links.size()) q->links[link] = ChestLink{};
-  if (q->wiener && link < q->wiener->slabs.size() && q->wiener->slabs[link]) return q->wiener->reset(link);
+  if (q->wiener && link < q->wiener->slabs.size() && q->wiener->slabs[link].p) return q->wiener->reset(link);
   return MI355_SUCCESS;
 }
 

@@ -5,6 +5,7 @@
 
 #include <vector>
 
+#include "device_mem.h"
 #include "wiener_internal.h"
 
 namespace mi355 {
@@ -12,10 +13,9 @@ namespace mi355 {
 struct WienerBank {
   int                device = 0;
   WienerDims         d{};
-  std::vector<char*> slabs; // per link, allocated (and initialised) on first use
-  float2*            d_tw = nullptr, *d_filter = nullptr;
-  char*              d_scratch   = nullptr;
-  size_t             scratch_cap = 0;
+  std::vector<DevMem> slabs; // per link, allocated (and initialised) on first use
+  DevMem             d_tw, d_filter; // float2
+  DevScratch         scratch;
 
   int init(int dev, uint32_t nof_prb, uint32_t ntx, uint32_t nrx);
   int reset(uint32_t link);
@@ -24,7 +24,7 @@ struct WienerBank {
   // out_stride per (rx, port)).  Asynchronous on s.
   int launch(const WienerJob* jobs, const uint32_t* link, uint32_t njobs, const uint32_t* shift, bool always,
              uint32_t out_stride, uint32_t o_noise, uint32_t o_rsrp, hipStream_t s);
-  ~WienerBank();
+  ~WienerBank() { (void)hipSetDevice(device); } // for the members' frees
 };
 
 } // namespace mi355

@@ -11,16 +11,8 @@
 
 #include "../../include/srsran_amd/tdec.h"
 #include "../../include/srsran_amd/wiener.h"
+#include "device_mem.h"
 #include "wiener_bank.h"
-
-#define CHECK_HIP(x)                                                                                                   \
-  do {                                                                                                                 \
-    hipError_t e_ = (x);                                                                                               \
-    if (e_ != hipSuccess) {                                                                                            \
-      fprintf(stderr, "[srsran_amd] %s:%d %s: %s\n", __FILE__, __LINE__, #x, hipGetErrorString(e_));                 \
-      return MI355_ERROR;                                                                                              \
-    }                                                                                                                  \
-  } while (0)
 
 namespace mi355 {
 
@@ -56,34 +48,23 @@ int WienerBank::init(int dev, uint32_t nof_prb, uint32_t ntx, uint32_t nrx)
     F[k] = make_float2(re, im);
   }
   CHECK_HIP(hipSetDevice(device));
-  CHECK_HIP(hipMalloc(&d_tw, WNR_MIN_RE * sizeof(float2)));
-  CHECK_HIP(hipMalloc(&d_filter, WNR_MIN_RE * sizeof(float2)));
-  CHECK_HIP(hipMemcpy(d_tw, tw.data(), WNR_MIN_RE * sizeof(float2), hipMemcpyHostToDevice));
-  CHECK_HIP(hipMemcpy(d_filter, F.data(), WNR_MIN_RE * sizeof(float2), hipMemcpyHostToDevice));
+  CHECK_HIP(d_tw.upload(tw));
+  CHECK_HIP(d_filter.upload(F));
   return MI355_SUCCESS;
-}
-
-WienerBank::~WienerBank()
-{
-  (void)hipSetDevice(device);
-  for (char* s : slabs)
-    if (s) (void)hipFree(s);
-  for (void* p : {(void*)d_tw, (void*)d_filter, (void*)d_scratch})
-    if (p) (void)hipFree(p);
 }
 
 // srslte_wiener_dl_init + set_cell: zeroed state, std::mt19937(0xdead) seeded as [rand.eng.mers] (mti = 624)
 int WienerBank::reset(uint32_t link)
 {
-  if (link >= slabs.size()) slabs.resize((size_t)link + 1, nullptr);
+  if (link >= slabs.size()) slabs.resize((size_t)link + 1);
   CHECK_HIP(hipSetDevice(device));
-  if (!slabs[link]) CHECK_HIP(hipMalloc(&slabs[link], d.slab_bytes));
-  CHECK_HIP(hipMemset(slabs[link], 0, d.slab_bytes));
+  if (!slabs[link].p) CHECK_HIP(slabs[link].alloc(d.slab_bytes));
+  CHECK_HIP(hipMemset(slabs[link].p, 0, d.slab_bytes));
   std::vector<uint32_t> mt(626, 0);
   mt[0] = 0xdead;
   for (uint32_t i = 1; i < 624; i++) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + i;
   mt[624] = 624; // mti
-  CHECK_HIP(hipMemcpy(slabs[link], mt.data(), 625 * sizeof(uint32_t), hipMemcpyHostToDevice));
+  CHECK_HIP(hipMemcpy(slabs[link].p, mt.data(), 625 * sizeof(uint32_t), hipMemcpyHostToDevice));
   return MI355_SUCCESS;
 }
 
@@ -99,7 +80,7 @@ int WienerBank::launch(const WienerJob* jobs, const uint32_t* link, uint32_t njo
   if (slot.size() <= maxl) slot.resize((size_t)maxl + 1, -1);
   std::vector<uint32_t> count;
   for (uint32_t i = 0; i < njobs; i++) {
-    if (link[i] >= slabs.size() || !slabs[link[i]]) {
+    if (link[i] >= slabs.size() || !slabs[link[i]].p) {
       const int r = reset(link[i]);
       if (r) return r;
     }
@@ -116,17 +97,14 @@ int WienerBank::launch(const WienerJob* jobs, const uint32_t* link, uint32_t njo
   std::vector<uint32_t> fill(first.begin(), first.end() - 1);
   for (uint32_t i = 0; i < njobs; i++) ljobs[fill[slot[link[i]]]++] = i;
   std::vector<char*> sl(nl);
-  for (uint32_t k = 0; k < nl; k++) sl[k] = slabs[order[k]];
+  for (uint32_t k = 0; k < nl; k++) sl[k] = slabs[order[k]].as<char>();
   // one device block: jobs | link_first | link_jobs | slabs
   const size_t bj = (size_t)njobs * sizeof(WienerJob), bf = (nl + 1) * 4, bl = (size_t)njobs * 4, bs = nl * sizeof(char*);
   const size_t o_f = (bj + 255) / 256 * 256, o_l = o_f + (bf + 255) / 256 * 256, o_s = o_l + (bl + 255) / 256 * 256;
   const size_t need = o_s + bs;
   CHECK_HIP(hipStreamSynchronize(s)); // the previous launch's descriptors may still be read
-  if (need > scratch_cap) {
-    if (d_scratch) CHECK_HIP(hipFree(d_scratch));
-    scratch_cap = need + need / 2;
-    CHECK_HIP(hipMalloc(&d_scratch, scratch_cap));
-  }
+  CHECK_HIP(scratch.reserve(need, need + need / 2, DevScratch::SyncFree));
+  char* d_scratch = scratch.base();
   CHECK_HIP(hipMemcpy(d_scratch, jobs, bj, hipMemcpyHostToDevice));
   CHECK_HIP(hipMemcpy(d_scratch + o_f, first.data(), bf, hipMemcpyHostToDevice));
   CHECK_HIP(hipMemcpy(d_scratch + o_l, ljobs.data(), bl, hipMemcpyHostToDevice));
@@ -136,8 +114,8 @@ int WienerBank::launch(const WienerJob* jobs, const uint32_t* link, uint32_t njo
   a.link_first = (const uint32_t*)(d_scratch + o_f);
   a.link_jobs  = (const uint32_t*)(d_scratch + o_l);
   a.slabs      = (char* const*)(d_scratch + o_s);
-  a.filter     = d_filter;
-  a.tw48       = d_tw;
+  a.filter     = d_filter.as<float2>();
+  a.tw48       = d_tw.as<float2>();
   a.d          = d;
   for (uint32_t p = 0; p < d.ntx; p++) a.shift[p] = shift[p];
   a.always     = always ? 1u : 0u;
@@ -157,8 +135,7 @@ struct mi355_wiener_dl {
   WienerBank  bank;
   uint32_t    nlinks = 0;
   hipStream_t own    = nullptr;
-  char*       d_io   = nullptr; // per-call snr | ready block, grow-only (no hipFree, which synchronises the device)
-  size_t      io_cap = 0;
+  DevScratch  d_io; // per-call snr | ready block, grow-only
 };
 
 extern "C" {
@@ -188,7 +165,6 @@ void mi355_wiener_dl_free(mi355_wiener_dl_t* q)
     (void)hipStreamSynchronize(q->own);
     (void)hipStreamDestroy(q->own);
   }
-  if (q->d_io) (void)hipFree(q->d_io);
   delete q;
 }
 
@@ -212,18 +188,9 @@ int mi355_wiener_dl_run_batch(mi355_wiener_dl_t* q, const uint32_t* link, uint32
   const uint32_t np = d.ntx * d.nrx;
   // snr and ready live in the object's grow-only device block: upload / read back around the launch
   const size_t part = ((size_t)njobs * np * 4 + 255) / 256 * 256;
-  if (2 * part > q->io_cap) {
-    if (q->d_io) {
-      CHECK_HIP(hipStreamSynchronize(s));
-      CHECK_HIP(hipFree(q->d_io));
-      q->d_io   = nullptr;
-      q->io_cap = 0;
-    }
-    CHECK_HIP(hipMalloc(&q->d_io, 2 * part + 256));
-    q->io_cap = 2 * part + 256;
-  }
-  float*   d_snr   = (float*)q->d_io;
-  int32_t* d_ready = (int32_t*)(q->d_io + part);
+  CHECK_HIP(q->d_io.reserve(2 * part, 2 * part + 256, DevScratch::SyncFree));
+  float*   d_snr   = (float*)q->d_io.base();
+  int32_t* d_ready = (int32_t*)(q->d_io.base() + part);
   int r = MI355_SUCCESS;
   if (hipMemcpy(d_snr, snr, (size_t)njobs * np * 4, hipMemcpyHostToDevice) != hipSuccess) r = MI355_ERROR;
   std::vector<WienerJob> jobs(njobs);
@@ -242,7 +209,7 @@ int mi355_wiener_dl_run_batch(mi355_wiener_dl_t* q, const uint32_t* link, uint32
   if (!r && ready && hipMemcpy(ready, d_ready, (size_t)njobs * np * 4, hipMemcpyDeviceToHost) != hipSuccess) r = MI355_ERROR;
   uint32_t draws = 0;
   if (!r && njobs &&
-      hipMemcpy(&draws, q->bank.slabs[link[0]] + offsetof(WienerLinkState, draws), 4, hipMemcpyDeviceToHost) != hipSuccess)
+      hipMemcpy(&draws, q->bank.slabs[link[0]].as<char>() + offsetof(WienerLinkState, draws), 4, hipMemcpyDeviceToHost) != hipSuccess)
     r = MI355_ERROR;
   return r ? r : (int)draws;
 }
