@@ -1,7 +1,7 @@
 // srsran_amd/csrc/pdcch_host.cpp -- host side of the downlink control channels: the REG map of a cell, the UE
 // search spaces, DCI payload sizes / packing / unpacking, the DL resource allocation (DCI -> PDSCH grant), the
-// replay of the UE's sequential blind search over the GPU-decoded candidates, and an eNodeB-side PCFICH /
-// PDCCH encoder for synthesising test subframes.
+// replay of the UE's sequential blind search over the GPU-decoded candidates, an eNodeB-side PCFICH /
+// PDCCH encoder for synthesising test subframes, and the PBCH's host functions (MIB packing, PBCH encoder).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,6 +13,7 @@
 #include "../../include/srsran_amd/pdcch.h"
 #include "lte_common.h"
 #include "lte_tbs_table.h"
+#include "pbch_internal.h"
 #include "pdcch_internal.h"
 
 namespace mi355 {
@@ -203,6 +204,32 @@ void precode_diversity(const std::vector<float2>& d, uint32_t ports, std::vector
       y[3][i + 3] = sc(conj(d[i + 2]));
     }
   }
+}
+
+// The tail-biting convolutional code (convcoder.c:42-68) of the F bits d and its rate matching to E bits: sub-block
+// interleaving of the 3 streams, circular bit collection (rm_conv.c:38-86)
+void conv_encode_rm(const uint8_t* d, uint32_t F, uint32_t E, std::vector<uint8_t>& e)
+{
+  static const uint32_t poly[3] = {0x6D, 0x4F, 0x57};
+  std::vector<uint8_t>  coded(3 * F);
+  uint32_t              sr = 0;
+  for (uint32_t i = F - 6; i < F; i++) sr = (sr << 1) | d[i];
+  for (uint32_t i = 0; i < F; i++) {
+    sr = (sr << 1) | d[i];
+    for (uint32_t j = 0; j < 3; j++) coded[3 * i + j] = (uint8_t)parity(sr & poly[j]);
+  }
+  const uint32_t nrows = (F + 31) / 32, Kp = 32 * nrows, ndummy = Kp - F;
+  std::vector<int16_t> w(3 * Kp);
+  for (uint32_t s = 0, k = 0; s < 3; s++)
+    for (uint32_t c = 0; c < 32; c++)
+      for (uint32_t r = 0; r < nrows; r++, k++) {
+        const uint32_t pos = r * 32 + kColPerm[c];
+        w[k]               = pos < ndummy ? (int16_t)-1 : (int16_t)coded[(pos - ndummy) * 3 + s];
+      }
+  e.resize(E);
+  for (uint32_t k = 0, j = 0; k < E; j = (j + 1) % (3 * Kp))
+    if (w[j] >= 0) e[k++] = (uint8_t)w[j];
+  (void)kColPermInv;
 }
 
 // REs of one PRB in one slot of a normal FDD subframe (ra_re_x_prb, ra_dl.c:46-174): the control region, PBCH and
@@ -982,30 +1009,12 @@ int mi355_pdcch_encode_host(const mi355_cell_t* cell, const mi355_dl_sf_cfg_t* s
   const uint32_t E = 72u << msg->location.L, F = msg->nof_bits + 16;
   if ((msg->location.ncce + (1u << msg->location.L)) * 9 > m.nregs[sf->cfi - 1]) return MI355_ERROR_INVALID_INPUTS;
   // CRC16 masked with the RNTI, tail-biting convolutional code (convcoder.c:42-68)
-  uint8_t d[PDCCH_MAX_F], coded[3 * PDCCH_MAX_F];
+  uint8_t d[PDCCH_MAX_F];
   memcpy(d, msg->payload, msg->nof_bits);
   const uint32_t crc = crc16(msg->payload, msg->nof_bits) ^ msg->rnti;
   for (uint32_t i = 0; i < 16; i++) d[msg->nof_bits + i] = (uint8_t)((crc >> (15 - i)) & 1u);
-  static const uint32_t poly[3] = {0x6D, 0x4F, 0x57};
-  uint32_t              sr      = 0;
-  for (uint32_t i = F - 6; i < F; i++) sr = (sr << 1) | d[i];
-  for (uint32_t i = 0; i < F; i++) {
-    sr = (sr << 1) | d[i];
-    for (uint32_t j = 0; j < 3; j++) coded[3 * i + j] = (uint8_t)parity(sr & poly[j]);
-  }
-  // rate matching: sub-block interleaving of the 3 streams, circular bit collection (rm_conv.c:38-86)
-  const uint32_t nrows = (F + 31) / 32, Kp = 32 * nrows, ndummy = Kp - F;
-  std::vector<int16_t> w(3 * Kp);
-  for (uint32_t s = 0, k = 0; s < 3; s++)
-    for (uint32_t c = 0; c < 32; c++)
-      for (uint32_t r = 0; r < nrows; r++, k++) {
-        const uint32_t pos = r * 32 + kColPerm[c];
-        w[k]               = pos < ndummy ? (int16_t)-1 : (int16_t)coded[(pos - ndummy) * 3 + s];
-      }
-  std::vector<uint8_t> e(E);
-  for (uint32_t k = 0, j = 0; k < E; j = (j + 1) % (3 * Kp))
-    if (w[j] >= 0) e[k++] = (uint8_t)w[j];
-  (void)kColPermInv;
+  std::vector<uint8_t> e;
+  conv_encode_rm(d, F, E, e);
   // scrambling at the candidate's offset, QPSK, transmit diversity, REG mapping from REG ncce*9
   std::vector<uint8_t> c;
   gold_sequence((sf->tti % 10) * 512 + cell->id, 72 * (msg->location.ncce) + E, c);
@@ -1017,6 +1026,69 @@ int mi355_pdcch_encode_host(const mi355_cell_t* cell, const mi355_dl_sf_cfg_t* s
   const uint32_t* re = &m.pdcch[sf->cfi - 1][36 * msg->location.ncce];
   for (uint32_t p = 0; p < cell->nof_ports; p++)
     for (uint32_t i = 0; i < E / 2; i++) reinterpret_cast<float2*>(sf_symbols[p])[re[i]] = y[p][i];
+  return MI355_SUCCESS;
+}
+
+// ---------------------------------------------------------------------------------------- PBCH (pbch.h)
+
+void mi355_pbch_mib_unpack(const uint8_t* msg, mi355_cell_t* cell, uint32_t* sfn)
+{
+  if (!msg || !cell) return;
+  auto take = [&](uint32_t n) { // srslte_bit_pack
+    uint32_t v = 0;
+    while (n--) v = (v << 1) | (*msg++ & 1u);
+    return v;
+  };
+  const uint32_t bw     = take(3);
+  cell->nof_prb         = bw == 0 ? 6 : bw == 1 ? 15 : (bw - 1) * 25;
+  cell->phich_length    = take(1) ? MI355_PHICH_EXT : MI355_PHICH_NORM;
+  cell->phich_resources = take(2); // MI355_PHICH_R_1_6, R_1_2, R_1, R_2 in the MIB's order
+  if (sfn) *sfn = take(8) << 2;
+}
+
+void mi355_pbch_mib_pack(const mi355_cell_t* cell, uint32_t sfn, uint8_t* payload)
+{
+  if (!cell || !payload) return;
+  memset(payload, 0, MI355_BCH_PAYLOAD_LEN);
+  uint8_t* msg = payload;
+  auto     put = [&](uint32_t v, uint32_t n) { // srslte_bit_unpack
+    for (uint32_t i = 0; i < n; i++) *msg++ = (uint8_t)((v >> (n - 1 - i)) & 1u);
+  };
+  put(cell->nof_prb <= 6 ? 0 : cell->nof_prb <= 15 ? 1 : 1 + cell->nof_prb / 25, 3);
+  put(cell->phich_length == MI355_PHICH_EXT, 1);
+  put(cell->phich_resources <= MI355_PHICH_R_2 ? cell->phich_resources : 0, 2);
+  put(sfn >> 2, 8);
+}
+
+int mi355_pbch_encode_host(const mi355_cell_t* cell, const uint8_t* bch_payload, float* const* sf_symbols,
+                           uint32_t frame_idx)
+{
+  if (!cell || !bch_payload || !sf_symbols || cell->nof_prb < 6 || cell->nof_prb > MI355_MAX_PRB ||
+      cell->cp != MI355_CP_NORM || !(cell->nof_ports == 1 || cell->nof_ports == 2 || cell->nof_ports == 4))
+    return MI355_ERROR_INVALID_INPUTS;
+  for (uint32_t p = 0; p < cell->nof_ports; p++)
+    if (!sf_symbols[p]) return MI355_ERROR_INVALID_INPUTS;
+  frame_idx %= 4;
+  // CRC16 with the port mask (srslte_crc_mask, pbch.c:42-45), tail-biting convolutional code, rate matching to the
+  // 1920 bits of four radio frames
+  static const uint32_t mask[5] = {0, 0x0000u, 0xFFFFu, 0, 0x5555u};
+  uint8_t               d[MI355_BCH_PAYLOADCRC_LEN];
+  for (uint32_t i = 0; i < MI355_BCH_PAYLOAD_LEN; i++) d[i] = bch_payload[i] & 1u;
+  const uint32_t crc = crc16(d, MI355_BCH_PAYLOAD_LEN) ^ mask[cell->nof_ports];
+  for (uint32_t i = 0; i < 16; i++) d[MI355_BCH_PAYLOAD_LEN + i] = (uint8_t)((crc >> (15 - i)) & 1u);
+  const uint32_t       nbits = 2 * MI355_PBCH_NOF_RE;
+  std::vector<uint8_t> e, c;
+  conv_encode_rm(d, MI355_BCH_PAYLOADCRC_LEN, 4 * nbits, e);
+  // this frame's 480 bits scrambled at their offset, QPSK, transmit diversity, srslte_pbch_put into every port
+  gold_sequence(cell->id, 4 * nbits, c);
+  std::vector<float2> sym(MI355_PBCH_NOF_RE);
+  for (uint32_t i = 0, o = frame_idx * nbits; i < MI355_PBCH_NOF_RE; i++)
+    sym[i] = qpsk(e[o + 2 * i] ^ c[o + 2 * i], e[o + 2 * i + 1] ^ c[o + 2 * i + 1]);
+  std::vector<float2> y[MI355_MAX_PORTS];
+  precode_diversity(sym, cell->nof_ports, y);
+  const std::vector<uint32_t> re = pbch_re(*cell);
+  for (uint32_t p = 0; p < cell->nof_ports; p++)
+    for (uint32_t i = 0; i < MI355_PBCH_NOF_RE; i++) reinterpret_cast<float2*>(sf_symbols[p])[re[i]] = y[p][i];
   return MI355_SUCCESS;
 }
 
