@@ -234,6 +234,26 @@ int mi355_ue_dl_find_and_decode_batch(mi355_ue_dl_t* q, mi355_softbuffer_pool_t*
 int mi355_ue_dl_ctrl_llr(mi355_ue_dl_t* q, uint32_t i, float* llr, uint32_t max_llr);
 int mi355_ue_dl_ctrl_candidates(mi355_ue_dl_t* q, uint32_t i, uint32_t* out, uint32_t max_words);
 
+/* Inspection of the convolutional-decoder wave the PDCCH blind search and the PBCH decoder share (parity tests at
+ * block lengths neither caller produces): one 64-lane wave per job runs the product kernels' own device routine on
+ * E host floats for an nbits-bit payload + CRC16.
+ *   mode 0  as the blind search after it has located a candidate: the mean-|LLR| gate (pdcch.c:392-397), then the
+ *           unscaled decoder reading the E values from device memory;
+ *   mode 1  as the PBCH decoder: the E values (<= 1920) staged in on-chip memory, dematched values multiplied by scale
+ *           before the quantisation (pbch.c:420).
+ * out: 8 words per job, a candidate record as mi355_ue_dl_ctrl_candidates returns them -- {status (1: gated out,
+ * 2: decoded), crc_rem, L = 0, ncce = 0, bits[4]}, everything past status zero when gated out.  Synchronous, on
+ * `device`.  MI355_ERROR_INVALID_INPUTS for nbits = 0, nbits > MI355_DCI_MAX_BITS, E = 0, an unknown mode or
+ * E > 1920 in mode 1 (nothing is launched then). */
+typedef struct {
+  const float* llr; /* E host floats */
+  uint32_t     E;
+  uint32_t     nbits;
+  uint32_t     mode;
+  float        scale; /* mode 1 only */
+} mi355_conv_job_t;
+int mi355_debug_conv_decode_batch(int device, const mi355_conv_job_t* jobs, uint32_t njobs, uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

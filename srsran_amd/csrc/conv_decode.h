@@ -339,7 +339,7 @@ __device__ __forceinline__ uint32_t decode_cand(WaveLds& S, const float* llr, ui
   // x^(nbits - 1 - i + 16) mod P, so every lane takes its bits' terms and the wave xor-reduces; the payload words
   // (MSB first) and the received parity come from ballots of the decoded bits -- no serial per-bit loop on one lane
   uint32_t rem = 0;
-  if (F > 128) { // (no LTE DCI is this long: MI355_DCI_MAX_BITS bounds the buffer) the serial form
+  if (F > 128) { // the serial form: no LTE DCI is this long, but MI355_DCI_MAX_BITS admits payloads of 113..128 bits
     if (lane == 0) {
       uint32_t crc = 0, p = 0;
       for (uint32_t i = 0; i < nbits; i++) {

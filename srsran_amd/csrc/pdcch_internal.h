@@ -103,6 +103,17 @@ hipError_t ctrl_launch_llr(const CtrlArgs& a, uint32_t njobs, hipStream_t s);
 hipError_t ctrl_launch_blind(const BlindArgs& a, uint32_t njobs, hipStream_t s);
 hipError_t ctrl_launch_compact(const CompactArgs& a, uint32_t njobs, hipStream_t s);
 
+// Inspection of the shared decoder wave (mi355_debug_conv_decode_batch): one wave per job
+constexpr uint32_t CONV_DEBUG_MAX_E_LDS = 1920; // mode 1 stages its input in LDS as pbch_decode does (4 x 480)
+struct ConvDebugJob {
+  uint64_t off;   // first of the job's E floats in llr
+  uint32_t E, nbits;
+  uint32_t mode;  // 0: gate_pass + decode_cand<false> from global memory; 1: decode_cand<true> from LDS
+  float    scale; // mode 1
+};
+hipError_t ctrl_launch_conv_debug(const ConvDebugJob* jobs, const float* llr, DciCand* out, uint32_t njobs,
+                                  hipStream_t s);
+
 // host search-space generation (pdcch.c:222-330), shared by the runtime's blind-search replay
 uint32_t ue_locations(uint32_t nof_cce, uint32_t Yk, mi355_dci_location_t* c);
 uint32_t common_locations(uint32_t nof_cce, mi355_dci_location_t* c);

@@ -10,6 +10,8 @@
 //                 modular compare), chainback and CRC16 -> the CRC remainder the host compares with the RNTI.
 //   pdcch_compact one wave per subframe: the candidates whose remainder is the searched RNTI, in slot order (the
 //                 only ones the host replay acts on) -> the small per-subframe record the host reads back.
+//   conv_decode_debug  inspection (mi355_debug_conv_decode_batch): one wave per caller-given vector through gate_pass /
+//                 decode_cand as pdcch_blind and pbch_decode call them, for parity tests at every block length.
 //
 // Integer / byte-level work throughout; nothing here is GEMM-shaped.  The equaliser evaluates the reference's
 // formulas without FMA contraction (built with -ffp-contract=off) so it equals oracle/orc_pdcch.c bit for bit.
@@ -192,7 +194,39 @@ __global__ __launch_bounds__(64 * WAVES) void pdcch_blind(BlindArgs a)
   decode_cand(lds[wv], llr, E, nbits, L, ncce, out, w0);
 }
 
+// Inspection (mi355_debug_conv_decode_batch): one wave per job through the routines the product kernels call.
+// Mode 0 is pdcch_blind from its gate on, mode 1 pbch_decode from its decode_cand<true> on (the vector in LDS).
+__global__ __launch_bounds__(64) void conv_decode_debug(const ConvDebugJob* jobs, const float* llr, DciCand* out)
+{
+  __shared__ WaveLds lds;
+  __shared__ float   s_vec[CONV_DEBUG_MAX_E_LDS];
+  const uint32_t     lane = threadIdx.x;
+  const ConvDebugJob J    = jobs[blockIdx.x];
+  const float*       in   = llr + J.off;
+  DciCand*           o    = out + blockIdx.x;
+  uint32_t           w0;
+  if (J.mode == 0) {
+    if (!gate_pass(in, J.E)) {
+      if (lane == 0) o->status = 1, o->L = 0, o->ncce = 0;
+      return;
+    }
+    decode_cand(lds, in, J.E, J.nbits, 0, 0, o, w0);
+  } else {
+    for (uint32_t j = lane; j < J.E && j < CONV_DEBUG_MAX_E_LDS; j += 64) s_vec[j] = in[j];
+    __syncthreads();
+    decode_cand<true>(lds, s_vec, min(J.E, CONV_DEBUG_MAX_E_LDS), J.nbits, 0, 0, o, w0, J.scale);
+  }
+}
+
 } // namespace
+
+hipError_t ctrl_launch_conv_debug(const ConvDebugJob* jobs, const float* llr, DciCand* out, uint32_t njobs,
+                                  hipStream_t s)
+{
+  if (!njobs) return hipSuccess;
+  hipLaunchKernelGGL(conv_decode_debug, dim3(njobs), dim3(64), 0, s, jobs, llr, out);
+  return hipGetLastError();
+}
 
 hipError_t ctrl_launch_llr(const CtrlArgs& a, uint32_t njobs, hipStream_t s)
 {

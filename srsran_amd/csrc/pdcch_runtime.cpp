@@ -252,3 +252,35 @@ int CtrlState::finish(uint32_t chunk, const uint16_t* rntis, const mi355_ue_dl_c
 }
 
 } // namespace mi355
+
+using namespace mi355;
+
+// The decoder wave of conv_decode.h on caller-given vectors (pdcch.h): the jobs' floats packed end to end, one
+// descriptor and one record per job, all in allocations this call owns and frees.
+int mi355_debug_conv_decode_batch(int device, const mi355_conv_job_t* jobs, uint32_t njobs, uint32_t* out)
+{
+  if (!njobs) return MI355_SUCCESS;
+  if (!jobs || !out) return MI355_ERROR_INVALID_INPUTS;
+  static_assert(sizeof(DciCand) == 32, "8 words per record");
+  std::vector<ConvDebugJob> dj(njobs);
+  size_t                    total = 0;
+  for (uint32_t i = 0; i < njobs; i++) {
+    const mi355_conv_job_t& j = jobs[i];
+    if (!j.llr || !j.E || !j.nbits || j.nbits > MI355_DCI_MAX_BITS || j.mode > 1 ||
+        (j.mode == 1 && j.E > CONV_DEBUG_MAX_E_LDS))
+      return MI355_ERROR_INVALID_INPUTS;
+    dj[i] = ConvDebugJob{total, j.E, j.nbits, j.mode, j.scale};
+    total += j.E;
+  }
+  std::vector<float> llr(total);
+  for (uint32_t i = 0; i < njobs; i++) memcpy(llr.data() + dj[i].off, jobs[i].llr, (size_t)jobs[i].E * 4);
+  CHECK_HIP(hipSetDevice(device));
+  DevMem d_jobs, d_llr, d_out;
+  CHECK_HIP(d_jobs.upload(dj));
+  CHECK_HIP(d_llr.upload(llr));
+  CHECK_HIP(d_out.alloc((size_t)njobs * sizeof(DciCand)));
+  CHECK_HIP(hipMemset(d_out.p, 0, d_out.bytes));
+  CHECK_HIP(ctrl_launch_conv_debug(d_jobs.as<ConvDebugJob>(), d_llr.as<float>(), d_out.as<DciCand>(), njobs, nullptr));
+  CHECK_HIP(hipMemcpy(out, d_out.p, d_out.bytes, hipMemcpyDeviceToHost));
+  return MI355_SUCCESS;
+}

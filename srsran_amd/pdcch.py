@@ -71,6 +71,11 @@ class CtrlRes(C.Structure):
     _fields_ = [("cfi", C.c_uint32), ("cfi_corr", C.c_float), ("nof_dci", C.c_int32), ("nof_cce", C.c_uint32)]
 
 
+class ConvJob(C.Structure):
+    _fields_ = [("llr", C.c_void_p), ("E", C.c_uint32), ("nbits", C.c_uint32), ("mode", C.c_uint32),
+                ("scale", C.c_float)]
+
+
 def _declare():
     L = _declare_ue_dl()
     if getattr(L, "_pdcch_declared", False):
@@ -99,6 +104,7 @@ def _declare():
                                                     P(PdschRes), vp]
     L.mi355_ue_dl_ctrl_llr.argtypes = [vp, u32, vp, u32]
     L.mi355_ue_dl_ctrl_candidates.argtypes = [vp, u32, vp, u32]
+    L.mi355_debug_conv_decode_batch.argtypes = [i32, P(ConvJob), u32, vp]
     L._pdcch_declared = True
     return L
 
@@ -226,3 +232,16 @@ def last_candidates(ue, i: int) -> np.ndarray:
     if n < 0:
         raise RuntimeError("ctrl_candidates failed")
     return out.view(CAND_DTYPE).reshape(22, 2)
+
+
+def conv_decode_debug(jobs, device: int = 0) -> np.ndarray:
+    """mi355_debug_conv_decode_batch: jobs are (llr, nbits, mode, scale) with llr the job's E float32 values; one
+    64-lane wave per job through the decoder the PDCCH blind search (mode 0: gate, unscaled) and the PBCH decoder
+    (mode 1: scaled, input in LDS) share.  Returns (n,) records of CAND_DTYPE."""
+    n = len(jobs)
+    keep = [np.ascontiguousarray(j[0], np.float32) for j in jobs]
+    arr = (ConvJob * n)(*[ConvJob(k.ctypes.data, k.size, int(j[1]), int(j[2]), float(j[3]))
+                          for k, j in zip(keep, jobs)])
+    out = np.zeros(n * 8, np.uint32)
+    check(_declare().mi355_debug_conv_decode_batch(device, arr, n, out.ctypes.data), "debug_conv_decode_batch")
+    return out.view(CAND_DTYPE)

@@ -21,15 +21,10 @@ def _dev(arr):
     return DeviceBuffer(a.nbytes).upload(a)
 
 
-def _region_jobs(k, Z):
-    from srsran_amd import pdsch as S
+def _host_job(y, h, sf, noise):
+    """One control-channel job from host grids y (rx, G) and estimates h (ports, rx, G): (job, chest, buffers)"""
     from srsran_amd.ue_dl import ChestRes, DlSfJob
-    nprb, ports, nrx, cid, sf, cfi = (int(v) for v in Z[f"sf{k}_cfg"])
-    glen = 14 * 12 * nprb
-    y = np.zeros((nrx, glen), np.complex64)
-    h = np.zeros((ports, nrx, glen), np.complex64)
-    c = Z[f"sf{k}_y"].shape[1]
-    y[:, :c], h[:, :, :c] = Z[f"sf{k}_y"], Z[f"sf{k}_h"]
+    nrx, ports = y.shape[0], h.shape[0]
     keep = [_dev(y[r]) for r in range(nrx)] + [_dev(h[p, r]) for p in range(ports) for r in range(nrx)]
     j = DlSfJob()
     j.tti = sf
@@ -38,8 +33,49 @@ def _region_jobs(k, Z):
         for p in range(ports):
             j.ce[p][r] = keep[nrx + p * nrx + r].ptr
     chest = (ChestRes * 1)()
-    chest[0].noise_estimate = float(Z[f"sf{k}_noise"])
+    chest[0].noise_estimate = noise
+    return j, chest, keep
+
+
+def _region_jobs(k, Z):
+    from srsran_amd import pdsch as S
+    nprb, ports, nrx, cid, sf, cfi = (int(v) for v in Z[f"sf{k}_cfg"])
+    glen = 14 * 12 * nprb
+    y = np.zeros((nrx, glen), np.complex64)
+    h = np.zeros((ports, nrx, glen), np.complex64)
+    c = Z[f"sf{k}_y"].shape[1]
+    y[:, :c], h[:, :, :c] = Z[f"sf{k}_y"], Z[f"sf{k}_h"]
+    j, chest, keep = _host_job(y, h, sf, float(Z[f"sf{k}_noise"]))
     return S.make_cell(nprb, ports, cid), nrx, j, chest, keep, y, h
+
+
+def _check_slots(cand, o_llr, ncce, sf, rnti, nb_ue, nb_com):
+    """Every one of the 22 slots x 2 sizes of a subframe's raw candidate results against the oracle on the same LLRs.
+    nb_ue / nb_com: the payload sizes tried per format slot in the UE-specific / common space (0: none; None: the
+    space is not searched).  Slots 0-15 list P.ue_locations in order, slots 16-21 P.common_locations; a slot past its
+    list, or a size not tried, has status 0; an occupied one carries its (L, ncce) and status 1 when the oracle's
+    mean-|LLR| gate skips it, else status 2 with the oracle's CRC remainder and payload.  Returns the status counts."""
+    ue = P.ue_locations(ncce, sf, rnti) if nb_ue else []
+    com = P.common_locations(ncce) if nb_com else []
+    count = [0, 0, 0]
+    assert cand.shape == (22, 2)
+    for s in range(22):
+        locs, nb, k = (ue, nb_ue, s) if s < 16 else (com, nb_com, s - 16)
+        for f in range(2):
+            c = cand[s, f]
+            if k >= len(locs) or not nb[f]:
+                assert c["status"] == 0, (s, f)
+                count[0] += 1
+                continue
+            L, n = locs[k]
+            ok, bits, crc = P.decode_candidate(o_llr, L, n, nb[f])
+            assert c["status"] == (2 if ok else 1) and (c["L"], c["ncce"]) == (L, n), (s, f)
+            count[int(c["status"])] += 1
+            if ok:
+                assert c["crc_rem"] == crc, (s, f)
+                got = np.unpackbits(c["bits"].astype(">u4").view(np.uint8))
+                assert np.array_equal(got[: nb[f]], bits) and not got[nb[f]:].any(), (s, f)
+    return count
 
 
 @pytest.mark.parametrize("k", range(8))
@@ -61,24 +97,79 @@ def test_control_region_goldens(k):
     assert np.array_equal(llr, o_llr)  # bit-exact with the oracle
     ref = Z[f"sf{k}_llr"]
     assert np.abs(llr - ref).max() <= 1e-5 * np.abs(ref).max()
-    # candidates: every slot's status / CRC remainder / payload equals the oracle's decode of the same LLRs
+    # candidates: every slot's status / location / CRC remainder / payload equals the oracle's decode of the same LLRs
+    # (UE-specific slots unused for the SI-RNTI, common slots past the list empty, gated-out slots status 1)
     cand = D.last_candidates(ue, 0)
     nb = [P.dci_sizeof(f, nprb, ports, P.DciCfg(is_not_ue_ss=True)) for f in (P.FORMAT1A, P.FORMAT1C)]
-    for s, (L, n) in enumerate(P.common_locations(rg.nof_cce(o_cfi))):
-        for f in range(2):
-            c = cand[16 + s, f]
-            ok, bits, crc = P.decode_candidate(o_llr, L, n, nb[f])
-            assert c["status"] == (2 if ok else 1) and (c["L"], c["ncce"]) == (L, n)
-            if ok:
-                assert c["crc_rem"] == crc
-                got = np.unpackbits(c["bits"].astype(">u4").view(np.uint8))[: nb[f]]
-                assert np.array_equal(got, bits)
+    count = _check_slots(cand, o_llr, rg.nof_cce(o_cfi), sf, P.SIRNTI, None, nb)
+    assert count[1] + count[2] == 2 * len(P.common_locations(rg.nof_cce(o_cfi)))
     found = P.find_dl_dci(o_llr, rg.nof_cce(o_cfi), sf, P.SIRNTI, nprb, ports)
     assert ctrl[0].nof_dci == len(found) == len(dcis[0])
     for d, f in zip(dcis[0], found):
         assert (d.format, d.location.L, d.location.ncce) == (f["format"], f["L"], f["ncce"])
         assert (d.type2_alloc.riv, d.tb[0].mcs_idx, d.tb[0].rv) == (f["dci"]["riv"], f["dci"]["tb"][0]["mcs_idx"],
                                                                     f["dci"]["tb"][0]["rv"])
+    ue.close()
+
+
+# ------------------------------------------------------------------ UE-specific search space at few CCEs
+
+# a fixed flat channel: one complex gain per transmit port
+FLAT_H = np.array([0.9 + 0.3j, -0.5 + 0.7j, 0.6 - 0.6j, -0.8 - 0.2j], np.complex64)
+# (nof_prb, ports, cfi, nof_cce): control regions of 1..6 CCEs, where levels drop out of the UE-specific search space
+# (N / L = 0) and a level's 6 / 6 / 2 / 2 candidates wrap onto fewer distinct ones
+SMALL_REGIONS = [(6, 1, 1, 2), (6, 1, 2, 4), (6, 1, 3, 6), (6, 4, 1, 1), (6, 4, 2, 3), (6, 4, 3, 5), (15, 2, 1, 2)]
+
+
+@pytest.mark.parametrize("nprb,ports,cfi,ncce", SMALL_REGIONS, ids=[f"{r[0]}prb_{r[1]}p_{r[3]}cce" for r in SMALL_REGIONS])
+def test_ue_space_slots_at_few_cces(nprb, ports, cfi, ncce):
+    """The device's own enumeration of the search spaces (slot_location, a closed form of pdcch.c:230-330 without the
+    candidate list) slot by slot against the oracle's lists, UE-specific slots 0-15 included, in control regions of
+    1..6 CCEs.  One format 1A DCI at a UE-specific location (the highest level in one subframe, the first candidate
+    in the other) over a flat channel; the search covers the UE-specific space and the common space."""
+    from srsran_amd import pdcch as D
+    from srsran_amd import pdsch as S
+    from srsran_amd.ue_dl import ChestRes, UeDl
+    cid, rnti, tm, sigma = 5, 0x3C1A, 0 if ports == 1 else 1, 0.02
+    cell = S.make_cell(nprb, ports, cid)
+    assert D.nof_cce(cell, cfi) == ncce
+    rg = P.regs(nprb, ports, cid, 0)
+    G = 14 * 12 * nprb
+    rng = np.random.default_rng(100 * nprb + 10 * ports + cfi)
+    jobs, keep, grids, noise = [], [], [], 2 * sigma * sigma
+    h = np.ascontiguousarray(np.broadcast_to(FLAT_H[:ports, None, None], (ports, 1, G)))
+    for sf, pick in ((1, -1), (6, 0)):
+        L, n = D.ue_locations(ncce, sf, rnti)[pick]
+        m = D.pack(cell, _make_dci(D, cell, P.FORMAT1A, 7, rnti), sf)
+        m.location, m.rnti = D.DciLocation(L, n), rnti
+        tx = np.zeros((ports, G), np.complex64)
+        D.encode_ctrl_host(cell, sf, cfi, [m], tx)
+        y = (FLAT_H[:ports, None] * tx).sum(axis=0) + sigma * (rng.standard_normal(G) + 1j * rng.standard_normal(G))
+        y = y.astype(np.complex64)[None, :]
+        j, _chest, k = _host_job(y, h, sf, noise)
+        jobs.append(j), keep.append(k), grids.append((sf, y, D.msg_bits(m)))
+    chest = (ChestRes * 2)()
+    chest[0].noise_estimate = chest[1].noise_estimate = noise
+    ucfg = D.UeDlCfg()
+    ucfg.tm, ucfg.dci_common_ss = tm, 1
+    ue = UeDl(cell, 1)
+    cfis, ctrl, dcis = D.find_dl_dci(ue, jobs, [rnti] * 2, [ucfg] * 2, chest)
+    nb_ue = [P.dci_sizeof(f, nprb, ports) for f in P.UE_FORMATS[tm]]
+    nb_com = [P.dci_sizeof(P.FORMAT1A, nprb, ports, P.DciCfg(is_not_ue_ss=True)), 0]
+    for i, (sf, y, sent) in enumerate(grids):
+        assert cfis[i] == cfi and ctrl[i].nof_cce == ncce
+        o_llr = P.pdcch_llr(y, h, rg, cfi, cid, sf, noise)
+        assert np.array_equal(D.last_llr(ue, i), o_llr)
+        count = _check_slots(D.last_candidates(ue, i), o_llr, ncce, sf, rnti, nb_ue, nb_com)
+        nloc = len(P.ue_locations(ncce, sf, rnti))
+        assert count[0] == 44 - 2 * nloc - len(P.common_locations(ncce)) and count[2] >= 1
+        found = P.find_dl_dci(o_llr, ncce, sf, rnti, nprb, ports, tm=tm, dci_common_ss=True)
+        assert len(found) >= 1 and np.array_equal(found[0]["bits"], sent)  # (the oracle itself finds what was sent)
+        assert ctrl[i].nof_dci == len(found) == len(dcis[i])
+        for d, f in zip(dcis[i], found):
+            assert (d.format, d.location.L, d.location.ncce) == (f["format"], f["L"], f["ncce"])
+            assert (d.type2_alloc.riv, d.tb[0].mcs_idx, d.tb[0].rv) == (f["dci"]["riv"], f["dci"]["tb"][0]["mcs_idx"],
+                                                                        f["dci"]["tb"][0]["rv"])
     ue.close()
 
 
