@@ -53,6 +53,7 @@ def lib() -> C.CDLL:
         L.orc_tdec_pack_input.argtypes = [i16p, C.c_uint32, i16p]
         L.orc_tdec_run.argtypes = [i16p, C.c_uint32, C.c_uint32, u8p, C.c_void_p, C.c_void_p]
         L.orc_tdec_run_generic.argtypes = [i16p, C.c_uint32, C.c_uint32, u8p]
+        L.orc_tdec_run_generic_trace.argtypes = [i16p, C.c_uint32, C.c_uint32, u8p, C.c_void_p]
         L.orc_tcod_encode.argtypes = [u8p, C.c_uint32, u8p]
         L.orc_crc.restype = C.c_uint32
         L.orc_crc.argtypes = [u8p, C.c_uint32, C.c_uint32, C.c_uint32]
@@ -248,8 +249,12 @@ def tdec_run(buf: np.ndarray, K: int, nhalf: int, trace: bool = False, llr: bool
     return res[0] if len(res) == 1 else tuple(res)
 
 
-def tdec_run_generic(lin: np.ndarray, K: int, nhalf: int) -> np.ndarray:
+def tdec_run_generic(lin: np.ndarray, K: int, nhalf: int, trace: bool = False):
     out = np.zeros(K // 8, np.uint8)
+    if trace:
+        tr = np.zeros((nhalf, K // 8), np.uint8)
+        assert lib().orc_tdec_run_generic_trace(np.ascontiguousarray(lin, np.int16), K, nhalf, out, tr.ctypes.data) == 0
+        return out, tr
     assert lib().orc_tdec_run_generic(np.ascontiguousarray(lin, np.int16), K, nhalf, out) == 0
     return out
 

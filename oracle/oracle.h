@@ -20,6 +20,7 @@ uint32_t orc_tdec_buf_len(uint32_t K);
 void     orc_tdec_pack_input(const int16_t* lin, uint32_t K, int16_t* buf);
 int      orc_tdec_run(const int16_t* buf, uint32_t K, uint32_t nhalf, uint8_t* out, uint8_t* trace, int16_t* llr_out);
 int      orc_tdec_run_generic(const int16_t* lin, uint32_t K, uint32_t nhalf, uint8_t* out);
+int      orc_tdec_run_generic_trace(const int16_t* lin, uint32_t K, uint32_t nhalf, uint8_t* out, uint8_t* trace);
 int      orc_tcod_encode(const uint8_t* bits, uint32_t K, uint8_t* out);
 uint32_t orc_crc(const uint8_t* bytes, uint32_t nbits, uint32_t poly, uint32_t order);
 int      orc_cbsegm(uint32_t tbs, uint32_t res[6]);

@@ -390,6 +390,12 @@ int orc_tdec_run(const int16_t* buf, uint32_t K, uint32_t nhalf, uint8_t* out, u
  * srslte_tdec_force_not_sb, the turbodecoder_test config-1 path). */
 int orc_tdec_run_generic(const int16_t* lin, uint32_t K, uint32_t nhalf, uint8_t* out)
 {
+  return orc_tdec_run_generic_trace(lin, K, nhalf, out, NULL);
+}
+
+/* trace (optional): nhalf x K/8 decision bytes, one row per half-iteration, as orc_tdec_run's */
+int orc_tdec_run_generic_trace(const int16_t* lin, uint32_t K, uint32_t nhalf, uint8_t* out, uint8_t* trace)
+{
   struct orc_tdec* d = tdec_new(K);
   if (!d || nhalf == 0) {
     if (d) tdec_del(d);
@@ -397,7 +403,12 @@ int orc_tdec_run_generic(const int16_t* lin, uint32_t K, uint32_t nhalf, uint8_t
   }
   d->nsb = 0;
   unpack(d, lin);
-  for (uint32_t n = 0; n < nhalf; n++) half_iteration(d, n);
+  for (uint32_t n = 0; n < nhalf; n++) {
+    half_iteration(d, n);
+    if (trace) {
+      decide(((n + 1) % 2) ? d->ext1 : d->app1, K, &trace[(size_t)n * (K / 8)]);
+    }
+  }
   decide((nhalf % 2) ? d->ext1 : d->app1, K, out);
   tdec_del(d);
   return 0;

@@ -78,6 +78,13 @@ class TdecBatch:
         check(lib().mi355_tdec_batch_run_dev(self.h, d_in, in_stride, n, K, nhalf, d_out,
                                              out_stride or K // 8, stream), "mi355_tdec_batch_run_dev")
 
+    def halfit_dev(self, d_in: int, in_stride: int, n: int, K: int, half_idx: int, d_out: int,
+                   out_stride: int | None = None, stream: int | None = None) -> None:
+        """Half-iteration half_idx alone (0 starts a decode, the workspace carries the state to the next call), the
+        decisions after it into d_out."""
+        check(lib().mi355_tdec_batch_halfit_dev(self.h, d_in, in_stride, n, K, half_idx, d_out,
+                                                out_stride or K // 8, stream), "mi355_tdec_batch_halfit_dev")
+
     def set_impl(self, impl: int) -> None:
         """0 = AUTO (by K, as the AVX2 build), 1 = GENERIC on the linear layout for every K."""
         check(lib().mi355_tdec_batch_set_impl(self.h, impl), "mi355_tdec_batch_set_impl")

@@ -37,6 +37,9 @@ Contents
   demod_extremes.npz (``make_golden.py demod_extremes``) srslte_demod_soft_demodulate_s and _b for every modulation
                      on symbols with a per-symbol gain from {1, 40, 300, 3e5, 1e9, 0}: int16 / int8 saturation, the
                      scalar tails' wrap and the x86 conversions' out-of-range result, n = 7, 16, 17, 100.
+  tdec8_sweep.npz    (``make_golden.py tdec8_sweep``) the 8-bit decoder at all 110 sizes it takes, on inputs regenerated
+                     from tests/tdec_inputs.py (random full-range int8, a codeword near the decoder's waterfall, one
+                     well above it): a 16-byte truncated SHA-256 of the decision bytes after each half-iteration 1..8.
 """
 from __future__ import annotations
 
@@ -361,6 +364,23 @@ def gen_demod_extremes(rng):
     print("demod_extremes.npz:", k, "cases")
 
 
+def gen_tdec8_sweep():
+    """The reference's 8-bit decoder at every size it takes (tests/tdec_inputs.py SIZES8) on the three input classes of
+    CLASSES8, regenerated from the integer generator there: per (K, class) the 16-byte truncated SHA-256 of the K/8
+    decision bytes after each half-iteration 1..8."""
+    import tdec_inputs as TI
+    Ks, names, dig = [], [], []
+    for K in TI.SIZES8:
+        tr = TI.ref_tdec8_traces(K)
+        for c in TI.CLASSES8:
+            Ks.append(K)
+            names.append(c)
+            dig.append(np.stack([TI.digest(tr[c][h]) for h in range(TI.NHALF)]))
+    data = {"K": np.array(Ks, np.int32), "cls": np.array(names), "digest": np.stack(dig)}
+    save_reproducible(os.path.join(OUT, "tdec8_sweep.npz"), data)
+    print("tdec8_sweep.npz:", len(Ks), "cases")
+
+
 def save_reproducible(path, data):
     """An .npz as np.savez_compressed writes it, with a fixed time stamp on every entry: the same arrays give the
     same bytes whenever the file is made."""
@@ -573,6 +593,9 @@ def main():
     if sys.argv[1:] == ["demod_extremes"]:
         gen_demod_extremes(np.random.default_rng(5005))
         return
+    if sys.argv[1:] == ["tdec8_sweep"]:
+        gen_tdec8_sweep()
+        return
     rng = np.random.default_rng(20201010)
     gen_tdec_auto(rng)
     gen_tdec_generic(rng)
@@ -584,6 +607,7 @@ def main():
     gen_tdec8(np.random.default_rng(8008))
     gen_ref_pins()
     gen_demod_extremes(np.random.default_rng(5005))
+    gen_tdec8_sweep()
 
 
 if __name__ == "__main__":

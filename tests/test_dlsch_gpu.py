@@ -2,10 +2,13 @@
 against the oracle's restatement of decode_tb (sch.c:363-570), whose rate matcher, decoder and CRC are
 pinned to the compiled reference by tests/golden/.  Bit-exact: return codes, payload bytes (including the
 trailing CB-CRC bytes), average iteration counts, HARQ softbuffer evolution."""
+import functools
+
 import numpy as np
 import pytest
 
 import oracle
+import tdec_inputs as TI
 from srsran_amd import check, lib
 from srsran_amd.dlsch import Dlsch, SoftbufferPool
 
@@ -174,3 +177,91 @@ def test_null_stream_reset_done_before_decode(kind):
         want = _oracle([noise], [(tbs, Qm, G, 0.0)], [0], 4, [oracle.Softbuffer()])
         _check(got, want, [(tbs, Qm, G, 0.0)])
         assert got[0] == [-1], (rnd, got[0])
+
+
+# ------------------------------------------------------------------ every code-block size on both turbo paths
+
+# channel SNR of each call: -1 / 0 / 1 dB, where blocks fail or converge late (at 1 dB every TB passes, none at its first
+# check), and one call in which TBs do pass at the first check (3 dB for one block, 4 dB for two)
+SWEEP_SNRS = {False: (-1.0, 0.0, 1.0, 3.0), True: (-1.0, 0.0, 1.0, 4.0)}
+SWEEP_ITS = 4
+TWO_BLOCK_SIZES = tuple(K for K in TI.CB_SIZES if K >= 3136)
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep(two_block: bool):
+    """Per channel SNR one call's worth of TBs, one per code-block size, and the oracle's decode of each from a
+    fresh softbuffer: [(cases, llrs, oracle results)].  Computed once for both parametrisations of dlsch_path."""
+    calls = []
+    for si, snr in enumerate(SWEEP_SNRS[two_block]):
+        rng = np.random.default_rng([188, int(two_block), si])
+        cases = []
+        for K in (TWO_BLOCK_SIZES if two_block else TI.CB_SIZES):
+            size = (2 * K - 72) if two_block else (K - 24)
+            sg = oracle.cbsegm(size)
+            assert (sg["C"], sg["K1"], sg["C2"], sg["F"]) == (2 if two_block else 1, K, 0, 0), (K, sg)
+            cases.append((size, 2, 3 * size + 120, snr))
+        llrs = [oracle.make_tb(rng, t, q, g, 0, s)[1] for (t, q, g, s) in cases]
+        want = _oracle(llrs, cases, [0] * len(cases), SWEEP_ITS, [oracle.Softbuffer(2) for _ in cases])
+        calls.append((cases, llrs, want))
+    return calls
+
+
+def _regime_counts(calls, two_block):
+    """{windows: [TBs that fail, that pass after more than one check, that pass at the first check]}"""
+    cnt = {0: [0, 0, 0], 8: [0, 0, 0], 16: [0, 0, 0]}
+    for cases, _llrs, want in calls:
+        for (tbs, *_r), (ret, _d, its) in zip(cases, want):
+            K = (tbs + 72) // 2 if two_block else tbs + 24
+            cnt[TI.nsb(K)][0 if ret != 0 else (1 if its > 1 else 2)] += 1
+    return cnt
+
+
+def _run_sweep(two_block):
+    import ctypes as C
+    calls = _sweep(two_block)
+    latency = lib().mi355_dlsch_set_latency_path(-1) > 0  # (a negative limit only reads the current one)
+    dl = Dlsch(0, SWEEP_ITS)
+    pool = SoftbufferPool(len(calls[0][0]), 2)
+    for cases, llrs, want in calls:
+        # every call within the default latency limit (and the fixture's): the latency parametrisation decodes
+        # every window-size block of it on tdec_win_lat, the throughput one none -- counted by the kernel itself
+        ncb = sum(oracle.cbsegm(t)["C"] for (t, *_r) in cases)
+        nwin = sum(oracle.cbsegm(t)["C"] for (t, *_r) in cases if TI.nsb(oracle.cbsegm(t)["K1"]))
+        assert ncb == len(cases) * (2 if two_block else 1) and ncb <= 256
+        assert nwin == (96 if two_block else 142)
+        pool.reset_all()
+        counters = (C.c_uint64 * 11)()
+        check(lib().mi355_dlsch_latency_profile(1, None), "latency_profile")
+        desc = [dict(tbs=t, Qm=q, rv=0, softbuffer=i) for i, (t, q, g, s) in enumerate(cases)]
+        try:
+            got = dl.decode(pool, desc, llrs)
+        finally:
+            check(lib().mi355_dlsch_latency_profile(0, C.addressof(counters)), "latency_profile")
+        assert counters[10] == (nwin if latency else 0), (counters[10], nwin, latency)  # [10]: code blocks it decoded
+        _check(got, want, cases)
+    dl.close()
+    pool.close()
+
+
+def test_dlsch_every_size_single_block():
+    """All 188 sizes as single-block TBs (tbs = K - 24, CRC24A), one call of 188 code blocks per channel SNR of -1 /
+    0 / 1 / 3 dB, 4 half-iterations at most: at every K the latency kernel (uneven halves for odd L, whole-byte DEC1
+    decisions for L % 16 == 0, every length of the last output chunk) and the throughput kernels meet blocks that
+    fail, that converge late and that pass at the first check.  Return codes, payload + CRC bytes and iteration counts
+    are the oracle's.  Reference condition, on the oracle: in each regime at least 5 TBs of each kind; observed (fail,
+    pass after more than one check, pass at the first): generic 20 / 104 / 60, 8 windows 27 / 79 / 22, 16 windows
+    128 / 293 / 19.  (At -1 / 0 / 1 dB alone no window-size TB passes at its first check, hence the 3 dB call.)"""
+    cnt = _regime_counts(_sweep(False), False)
+    assert all(min(v) >= 5 for v in cnt.values()), cnt
+    _run_sweep(False)
+
+
+def test_dlsch_every_size_two_blocks():
+    """Every K >= 3136 as a two-block TB (tbs = 2 K - 72: CRC24B per block and the TB's CRC24A), 96 code blocks per
+    call, at -1 / 0 / 1 / 4 dB.  Observed on the oracle: 73 TBs fail, 101 pass after more than one check, 18 at the
+    first check of both blocks."""
+    assert len(TWO_BLOCK_SIZES) == 48
+    cnt = _regime_counts(_sweep(True), True)
+    assert cnt[0] == cnt[8] == [0, 0, 0] and min(cnt[16]) >= 5, cnt
+    _run_sweep(True)

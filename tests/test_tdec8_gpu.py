@@ -8,6 +8,8 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+import oracle
+import tdec_inputs as TI
 from srsran_amd.tdec import DeviceBuffer, Tdec8Batch
 from tests.golden_io import load
 
@@ -68,3 +70,41 @@ def test_rm_turbo_rx_8bit_matches_reference_goldens():
         assert dec.rm_rx_dev(d_e2.ptr, E, E, d_out.ptr, blen, 1, K, (rv + 2) % 4) == 0
         got2 = d_out.download(np.zeros(blen, np.int8))
         assert np.array_equal(got2, z[f"rm{i}_out2"]), (K, rv, E, "harq")
+
+
+def test_tdec8_every_size_matches_reference_digests():
+    """All 110 sizes the 8-bit decoder takes (tests/golden/tdec8.npz holds 6): random full-range int8, a codeword
+    near the decoder's waterfall and one well above it (tests/tdec_inputs.py, regenerated here), one run_dev per K
+    with the trace buffer; the decision bytes after each half-iteration 1..8 must hash to the digests recorded from
+    the reference's decoders (tests/golden/tdec8_sweep.npz; tests/test_tdec_sweep_oracle.py pins them to the reference
+    where that is built)."""
+    z = load("tdec8_sweep.npz")
+    want = {(int(k), str(c)): d for k, c, d in zip(z["K"], z["cls"], z["digest"])}
+    assert len(want) == len(TI.SIZES8) * len(TI.CLASSES8)
+    dec = Tdec8Batch()
+    nh, nc = TI.NHALF, len(TI.CLASSES8)
+    kmax = max(TI.SIZES8)
+    smax = (3 * (kmax + 32) + 12 + 255) // 256 * 256
+    d_in, d_out, d_tr = DeviceBuffer(nc * smax), DeviceBuffer(nc * (kmax // 8)), DeviceBuffer(nc * nh * (kmax // 8))
+    bad = []
+    for K in TI.SIZES8:
+        blen = 3 * (K + 32) + 12
+        stride = (blen + 255) // 256 * 256
+        host = np.zeros((nc, stride), np.int8)
+        for r, c in enumerate(TI.CLASSES8):
+            host[r, :blen] = TI.block8(K, c)[1]
+        d_in.upload(host)
+        assert dec.run_dev(d_in.ptr, stride, nc, K, nh, d_out.ptr, K // 8, d_tr.ptr) == 0
+        tr = d_tr.download(np.zeros((nc, nh, K // 8), np.uint8))
+        out = d_out.download(np.zeros((nc, K // 8), np.uint8))
+        for r, c in enumerate(TI.CLASSES8):
+            for h in range(nh):
+                if not np.array_equal(TI.digest(tr[r, h]), want[(K, c)][h]):
+                    ref = TI.ref_tdec8_traces(K) if oracle.ref_available() else None  # (only to describe a mismatch)
+                    nbits = int(np.unpackbits(tr[r, h] ^ ref[c][h]).sum()) if ref else None
+                    bad.append(dict(K=K, cls=c, first_half_iteration=h + 1, differing_bits=nbits))
+                    break
+            else:
+                if not np.array_equal(out[r], tr[r, nh - 1]):
+                    bad.append(dict(K=K, cls=c, first_half_iteration="out"))
+    assert not bad, (len(bad), bad[:10])
