@@ -64,7 +64,8 @@ int mi355_softbuffer_cb_crc_dev(mi355_softbuffer_pool_t* p, uint32_t sb, const u
 typedef struct {
   uint32_t tbs;         /* transport block size in bits (grant.tb[i].tbs) */
   uint32_t nof_e_bits;  /* coded LLRs of the codeword (grant.tb[i].nof_bits) */
-  uint32_t Qm;          /* bits per symbol x layers of this codeword (sch.c:598-603: Qm * Nl) */
+  uint32_t Qm;          /* bits per symbol x layers of this codeword (sch.c:598-603: Qm * Nl); any value > 0, odd ones
+                           included (odd per-code-block LLR counts and offsets), as the reference's decode_tb */
   uint32_t rv;          /* redundancy version 0..3 */
   uint32_t softbuffer;  /* softbuffer index in the pool */
   uint64_t e_offset;    /* int16 offset of the codeword's LLRs in d_e_bits */

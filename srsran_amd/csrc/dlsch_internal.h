@@ -23,11 +23,16 @@ struct CbDesc {      // one code block of one transport block
   uint32_t tb, cb, C; // transport block index in the call, CB index, CBs in the TB
   uint32_t rlen;      // K - 24 (C > 1) or K
   uint32_t rp, n_e;   // offset / count of its LLRs in the TB's e_bits (sch.c:391-401)
-  uint32_t rv;
+  // two 16-bit fields in the word rv had, so that the descriptor stays 48 bytes: rv <= 3 (the planner rejects others)
+  // and nb <= K / 8 <= 768 both fit
+  uint16_t rv;
+  uint16_t nb;        // payload bytes it leaves at cb * rlen / 8: up to where the next CB starts (the last: K / 8)
   uint32_t slot;      // softbuffer code-block slot in the pool
   uint64_t e_off;     // element offset of the TB's LLRs in the e_bits buffer
   uint64_t data_off;  // byte offset of the TB payload in the data buffer
 };
+
+static_assert(sizeof(CbDesc) == 48, "CbDesc is read by every check kernel: keep it at three 16-byte words");
 
 struct TbDesc {
   uint32_t tbs, C, C1, K1, K2, slot0, invalid;

@@ -50,10 +50,19 @@ __device__ __forceinline__ uint32_t ld_llr_pair(const int16_t* e, uint32_t r2, b
   return al4 ? ((const uint32_t*)e)[r2] : ((uint32_t)(uint16_t)e[2 * r2] | ((uint32_t)(uint16_t)e[2 * r2 + 1] << 16));
 }
 
+// LLR pair r2 of the first n LLRs of e: a pair past them reads as zero, and so does the upper half of the pair that
+// holds the last LLR of an odd n (odd Qm), which is loaded alone (e[n] may lie past the caller's buffer)
+__device__ __forceinline__ uint32_t ld_llr_pair_n(const int16_t* e, uint32_t r2, uint32_t n, bool al4)
+{
+  if (2 * r2 + 1 < n) return ld_llr_pair(e, r2, al4);
+  return 2 * r2 < n ? (uint32_t)(uint16_t)e[2 * r2] : 0u;
+}
+
 // Every load of a thread is issued up front (inverse table, LLRs, old softbuffer words: fully unrolled,
 // independent of one another, 16 bytes per lane), so a block pays the memory latency about twice instead of
-// once per loop trip; the decoder buffer is written with 16-byte stores.  Qm is even, so n_e, rp and N are
-// even and the LLRs are handled as int16 pairs.
+// once per loop trip; the decoder buffer is written with 16-byte stores.  N is even and the LLRs are handled as
+// int16 pairs; with an odd Qm (the reference's decode_tb takes any) n_e and rp can be odd: the last LLR of a pass is
+// then half a pair (ld_llr_pair_n), and the 16-byte load path is left to the even counts.
 __global__ __launch_bounds__(RM_THREADS) void dlsch_rm_rx(DlschRmArgs a)
 {
   extern __shared__ __attribute__((aligned(16))) uint32_t acc32[]; // a.fold2 pairs, padded (img_u32)
@@ -69,12 +78,12 @@ __global__ __launch_bounds__(RM_THREADS) void dlsch_rm_rx(DlschRmArgs a)
     if (b >= a.ncb) break;
     const CbDesc& d = a.desc[b];
     if (a.sb_crc[d.slot]) continue; // CB already decoded in an earlier transmission (sch.c:385)
-    const uint32_t n_e = d.n_e, first2 = min(n_e, N) / 2;
+    const uint32_t n_e = d.n_e, first = min(n_e, N), first2 = first / 2;
     const bool     fresh = a.fresh[d.slot] != 0;
     uint32_t*      sb    = (uint32_t*)(a.sb + (size_t)d.slot * a.sb_stride);
     const bool     sb16  = ((uintptr_t)sb & 15) == 0;
     const int16_t* e     = a.e + d.e_off + d.rp;
-    const bool     e4    = ((uintptr_t)e & 3) == 0, e16 = ((uintptr_t)e & 15) == 0;
+    const bool     e4    = ((uintptr_t)e & 3) == 0, e16 = ((uintptr_t)e & 15) == 0 && !(first & 1);
     if (d.rv != iv_rv) {
       const uint32_t* inv32 = (const uint32_t*)a.inv[d.rv]; // hipMalloc'd: 16-byte aligned
 #pragma unroll
@@ -89,10 +98,8 @@ __global__ __launch_bounds__(RM_THREADS) void dlsch_rm_rx(DlschRmArgs a)
       if (e16) {
         ev[k] = ld_quad((const uint32_t*)e, q, first2, true, 0u);
       } else {
-        ev[k] = make_uint4(4 * q < first2 ? ld_llr_pair(e, 4 * q, e4) : 0u,
-                           4 * q + 1 < first2 ? ld_llr_pair(e, 4 * q + 1, e4) : 0u,
-                           4 * q + 2 < first2 ? ld_llr_pair(e, 4 * q + 2, e4) : 0u,
-                           4 * q + 3 < first2 ? ld_llr_pair(e, 4 * q + 3, e4) : 0u);
+        ev[k] = make_uint4(ld_llr_pair_n(e, 4 * q, first, e4), ld_llr_pair_n(e, 4 * q + 1, first, e4),
+                           ld_llr_pair_n(e, 4 * q + 2, first, e4), ld_llr_pair_n(e, 4 * q + 3, first, e4));
       }
     }
 #pragma unroll
@@ -123,9 +130,9 @@ __global__ __launch_bounds__(RM_THREADS) void dlsch_rm_rx(DlschRmArgs a)
     // later wraps (E > N) accumulate
     for (uint32_t base = N; base < n_e; base += N) {
       __syncthreads();
-      const uint32_t lim2 = min(N, n_e - base) / 2;
-      for (uint32_t r2 = tid; r2 < lim2; r2 += RM_THREADS)
-        acc32[img_u32(r2)] = add_pairs(acc32[img_u32(r2)], ld_llr_pair(e + base, r2, e4));
+      const uint32_t lim = min(N, n_e - base);
+      for (uint32_t r2 = tid; 2 * r2 < lim; r2 += RM_THREADS)
+        acc32[img_u32(r2)] = add_pairs(acc32[img_u32(r2)], ld_llr_pair_n(e + base, r2, lim, e4));
     }
     __syncthreads();
 #pragma unroll
@@ -169,7 +176,8 @@ __global__ __launch_bounds__(256) void dlsch_rm_consume(const CbDesc* desc, int 
 // After half-iteration h (sch.c:415-450): decision bytes -> CRC24B (C>1) or CRC24A over tbs+24 = K bits
 // (C==1); CRC ok => the CB is finished at this iteration.  Decision bytes of CB i land at i*rlen/8 of the
 // TB payload; only the last CB keeps its trailing CRC bytes (the earlier ones are overwritten by the
-// next CB in the reference's sequential loop, sch.c:422-424).
+// next CB in the reference's sequential loop, sch.c:422-424): CbDesc::nb bytes per CB, so that code blocks
+// checked in different launches never write the same byte.
 // "work remains" flags instead of a counter: running[h] != 0 iff some code block is unfinished before
 // half-iteration h (flag_set, crc_device.h; writers aggregate per workgroup).
 // When the window decoder writes decision bytes itself, it runs this check in its own epilogue (tdec_kernels.hip
@@ -202,7 +210,7 @@ __global__ __launch_bounds__(1024) void dlsch_cb_check(DlschCheckArgs a)
       if (lane == 0) unfinished = 1;
     } else {
       uint8_t*       dst = a.data + d.data_off + (size_t)d.cb * d.rlen / 8;
-      const uint32_t nb  = (d.cb + 1 == d.C) ? a.K / 8 : d.rlen / 8;
+      const uint32_t nb  = d.nb;
       for (uint32_t i = lane; i < nb; i += 64) dst[i] = dec[i];
       if (lane == 0) {
         a.its[b] = a.h + 1;
@@ -248,7 +256,12 @@ __global__ __launch_bounds__(256) void dlsch_tb_prologue(DlschTbArgs a)
       }
       const uint32_t g    = c < tb.C1 ? tb.cb_base[0] + c : tb.cb_base[1] + (c - tb.C1);
       const uint32_t slot = tb.slot0 + c;
-      a.desc[g]           = CbDesc{(uint32_t)t, c, tb.C, rlen, rp, n_e2, tb.rv, slot, tb.e_off, tb.data_off};
+      // The reference copies K / 8 bytes per CB in CB order, so a byte belongs to the last CB that covers it: CB c
+      // keeps [c rlen / 8, (c + 1) rlen' / 8) with rlen' the NEXT CB's (smaller at the K1 -> K2 boundary of a TB with
+      // two code-block sizes, whose first K2 block starts inside the last K1 block's bytes)
+      const uint32_t Kn   = c + 1 < tb.C1 ? tb.K1 : tb.K2;
+      const uint32_t nb   = c + 1 == tb.C ? K / 8 : (c + 1) * (Kn - 24) / 8 - c * rlen / 8;
+      a.desc[g]           = CbDesc{(uint32_t)t, c, tb.C, rlen, rp, n_e2, (uint16_t)tb.rv, (uint16_t)nb, slot, tb.e_off, tb.data_off};
       a.slot[g]           = slot;
       a.its[g]            = 0;
       const bool prior    = a.sb_crc[slot] != 0;

@@ -753,7 +753,7 @@ int mi355::dlsch_decode_dev_hook(mi355_dlsch_t* q, mi355_softbuffer_pool_t* pool
     const uint32_t emax = in.Qm * (in.nof_e_bits / in.Qm / seg.C + 1);
     auto           fold = [&](uint32_t g, uint32_t K) {
       if (fold2.size() <= g) fold2.resize(g + 1, 0);
-      fold2[g] = std::max(fold2[g], std::min(emax, 3 * K + 12) / 2);
+      fold2[g] = std::max(fold2[g], (std::min(emax, 3 * K + 12) + 1) / 2); // (an odd E: its last LLR is half a pair)
     };
     if (seg.C1) {
       const uint32_t g = group_of(seg.K1);

@@ -160,7 +160,7 @@ __device__ __forceinline__ void tdec_fused_check(const TdecWinArgs& a, int cb, i
     // payload bytes [0, nb) to dst (any alignment: cb * rlen / 8): the unaligned head and tail byte by byte (the
     // neighbouring code blocks' bytes share those words), the rest as dwords cut from two LDS words by alignbyte
     uint8_t*       dst  = c.data + d.data_off + (size_t)d.cb * d.rlen / 8;
-    const uint32_t nb   = (d.cb + 1 == d.C) ? nbytes : d.rlen / 8;
+    const uint32_t nb   = d.nb;
     const uint32_t head = min(nb, (4u - (uint32_t)((uintptr_t)dst & 3u)) & 3u);
     const uint32_t nw   = (nb - head) / 4, tail0 = head + 4 * nw;
     for (uint32_t i = l; i < head; i += NL) dst[i] = bytes[i];

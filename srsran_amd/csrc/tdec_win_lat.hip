@@ -729,7 +729,7 @@ __global__ __launch_bounds__(256) void tdec_win_lat(TdecLatArgs A)
       const bool     fin = ok || h + 1 == C.max_its || sflg[4];
       if (fin) {
         uint8_t*       dstp = C.data + d.data_off + (size_t)d.cb * d.rlen / 8;
-        const uint32_t nb   = (d.cb + 1 == d.C) ? (uint32_t)K / 8 : d.rlen / 8;
+        const uint32_t nb   = d.nb;
         for (uint32_t i = t; i < nb; i += 64) dstp[i] = dec[i];
         if (t == 0) {
           C.its[cb] = h + 1;

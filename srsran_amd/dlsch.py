@@ -84,14 +84,26 @@ class Dlsch:
     def set_max_iterations(self, n: int):
         check(self.L.mi355_dlsch_set_max_iterations(self.h, n), "set_max_iterations")
 
-    def decode(self, pool: SoftbufferPool, tbs: list[dict], e_bits: list[np.ndarray], llr8: bool = False):
+    def decode(self, pool: SoftbufferPool, tbs: list[dict], e_bits: list[np.ndarray], llr8: bool = False,
+               e_pad: list[int] | None = None):
         """tbs[i] = dict(tbs, Qm, rv, softbuffer); e_bits[i] = int16 LLRs of TB i (int8 with llr8: the
-        pdsch_8bit_decoder mode, mi355_dlsch_decode8_dev).  Returns (ret[i], data[i] bytes (tbs/8 + 6),
-        avg_iterations[i])."""
+        pdsch_8bit_decoder mode, mi355_dlsch_decode8_dev).  e_pad[i] (optional): unused LLR slots left in front of
+        TB i in the device buffer (256-byte aligned), so that its e_offset takes any alignment; default: the TBs
+        back to back.  Returns (ret[i], data[i] bytes (tbs/8 + 6), avg_iterations[i])."""
         n = len(tbs)
         dt = np.int8 if llr8 else np.int16
-        offs = np.cumsum([0] + [e.size for e in e_bits])
-        allE = np.concatenate([np.ascontiguousarray(e, dt) for e in e_bits]) if n else np.zeros(1, dt)
+        if e_pad is None:
+            offs = np.cumsum([0] + [e.size for e in e_bits])
+            allE = np.concatenate([np.ascontiguousarray(e, dt) for e in e_bits]) if n else np.zeros(1, dt)
+        else:
+            assert len(e_pad) == n
+            offs = np.zeros(n + 1, np.int64)
+            for i, e in enumerate(e_bits):
+                offs[i] += e_pad[i]
+                offs[i + 1] = offs[i] + e.size
+            allE = np.zeros(max(int(offs[-1]), 1), dt)
+            for i, e in enumerate(e_bits):
+                allE[offs[i]: offs[i] + e.size] = e
         doff = np.cumsum([0] + [t["tbs"] // 8 + 8 for t in tbs])
         d_e = DeviceBuffer(max(allE.nbytes, 2), self.device).upload(allE)
         d_data = DeviceBuffer(max(int(doff[-1]), 1), self.device)

@@ -193,3 +193,21 @@ def pool_softbuffer_check(pool, sb: int, want: np.ndarray, tbs: int, what=None):
                 if oracle.lib().orc_tdec_nsb(K) else np.r_[0:3 * K + 12])  # sub-block layout or the natural one
         w = want[c * 18600:(c + 1) * 18600]
         assert np.array_equal(got[c, cols], w[cols]), (what, c, int(np.abs(got[c, cols].astype(np.int32) - w[cols]).max()))
+
+
+def dirty_pool(pool, dl=None):
+    """Every code-block slot of a SoftbufferPool filled with -32768 by a dense transmission of max_cb blocks of
+    K = 6144 per softbuffer (E = N each), then reset: memory that a fresh rate dematching leaves unwritten, and that no
+    reader may take for data, no longer happens to hold zeros.  dl: a Dlsch to run it on (default: one of its own)."""
+    from srsran_amd.dlsch import Dlsch
+    C = pool.max_cb
+    tbs = 6120 if C == 1 else 6120 * C - 24  # B' = 6144 C: C blocks of 6144, no filler bits
+    own = dl is None
+    dl = Dlsch(0, 1) if own else dl
+    e = np.full(C * (3 * 6144 + 12), -32768, np.int16)
+    rets, _d, _i = dl.decode(pool, [dict(tbs=tbs, Qm=2, rv=0, softbuffer=i) for i in range(pool.nof_sb)],
+                             [e] * pool.nof_sb)
+    assert -2 not in rets
+    pool.reset_all()
+    if own:
+        dl.close()

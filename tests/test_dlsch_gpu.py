@@ -24,8 +24,10 @@ def dlsch_path(request):
     yield
     lib().mi355_dlsch_set_latency_path(old)
 
-# (tbs, Qm, G, snr_db): SISO QPSK MCS9 (C=3, K=5312), TM4 QAM256 MCS27 codeword (C=16, K=6144),
-# gamma != 0 cases, 16-window and 8-window and generic single-CB sizes
+# (tbs, Qm, G, snr_db): SISO QPSK MCS9 (C=3, K=5312), TM4 QAM256 MCS27 codeword (C=16, K=6144), a C=5 TB, one TB
+# with gamma != 0 (75376: C=13, G' % C = 9; every other case has C = 1 or G' % C = 0, so gamma = 0 -- 6120 / 14402 only
+# leaves G % Qm = 2 LLRs unused; gamma over C and two-size TBs are swept in test_rm_sweep_gpu.py), 16-window and
+# 8-window and generic single-CB sizes
 CASES = [(15840, 2, 30000, 3.0), (97896, 8, 115200, 9.0), (97896, 8, 115200, 5.5), (30576, 6, 36300, 4.5),
          (1000, 2, 3010, 1.0), (456, 2, 1500, 0.5), (40, 2, 200, -1.0), (6120, 4, 14402, 2.0),
          (75376, 6, 86400, 5.0), (2600, 2, 7800, 0.0),
