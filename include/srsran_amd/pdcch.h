@@ -18,7 +18,8 @@
  *   mi355_dci_* / mi355_ra_*        host functions of phch/dci.c, phch/ra.c, phch/ra_dl.c and the search
  *                                   spaces of phch/pdcch.c:222-330.
  *
- * Scope: FDD, normal CP, normal subframes (no MBSFN / TDD special subframes); PHICH mi = 1.  The structs
+ * Scope: FDD, normal CP, normal subframes (no MBSFN / TDD special subframes); PHICH mi = 1.  The format-0 (UL grant)
+ * messages the blind search comes across and PHICH decoding are in phich.h.  The structs
  * mirror srslte_dci_cfg_t, srslte_dci_location_t, srslte_dci_msg_t, srslte_dci_dl_t (phch/dci.h:49-130) and
  * srslte_ue_dl_cfg_t (ue/ue_dl.h:115-130) field by field.
  * Numerics: the CFI and every decoded DCI are the reference's for the same grid / channel estimates; PDCCH

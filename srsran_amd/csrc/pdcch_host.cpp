@@ -1,7 +1,8 @@
 // srsran_amd/csrc/pdcch_host.cpp -- host side of the downlink control channels: the REG map of a cell, the UE
 // search spaces, DCI payload sizes / packing / unpacking, the DL resource allocation (DCI -> PDSCH grant), the
 // replay of the UE's sequential blind search over the GPU-decoded candidates, an eNodeB-side PCFICH /
-// PDCCH encoder for synthesising test subframes, and the PBCH's host functions (MIB packing, PBCH encoder).
+// PDCCH encoder for synthesising test subframes, the PBCH's host functions (MIB packing, PBCH encoder) and the PHICH's
+// (group count, resource calculation, PHICH encoder) with DCI format 0 packing / unpacking.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../include/srsran_amd/pdcch.h"
+#include "../../include/srsran_amd/phich.h"
 #include "lte_common.h"
 #include "lte_tbs_table.h"
 #include "pbch_internal.h"
@@ -277,6 +279,15 @@ uint32_t re_x_prb(const mi355_cell_t& c, uint32_t sf_idx, uint32_t cfi, uint32_t
 
 // ---------------------------------------------------------------------------------------- REG map
 
+uint32_t phich_ngroups(const mi355_cell_t& cell, uint32_t phich_mi)
+{
+  const float ng = cell.phich_resources == MI355_PHICH_R_1_6   ? (float)1 / 6
+                   : cell.phich_resources == MI355_PHICH_R_1_2 ? (float)1 / 2
+                   : cell.phich_resources == MI355_PHICH_R_1   ? 1.0f
+                                                               : 2.0f;
+  return phich_mi * (uint32_t)ceilf(ng * ((float)cell.nof_prb / 8));
+}
+
 // srslte_regs_init_opts (regs.c:650-735): REGs numbered symbol-first inside each PRB, then the PCFICH
 // (regs.c:466-495), PHICH (regs.c:219-330) and per-CFI PDCCH sub-block interleaving (regs.c:62-150).
 bool regs_build(const mi355_cell_t& cell, uint32_t phich_mi, RegMap& m)
@@ -324,11 +335,7 @@ bool regs_build(const mi355_cell_t& cell, uint32_t phich_mi, RegMap& m)
   // PHICH groups (normal duration; extended uses one REG per symbol)
   m.phich.clear();
   if (phich_mi > 0) {
-    const float ng = cell.phich_resources == MI355_PHICH_R_1_6   ? (float)1 / 6
-                     : cell.phich_resources == MI355_PHICH_R_1_2 ? (float)1 / 2
-                     : cell.phich_resources == MI355_PHICH_R_1   ? 1.0f
-                                                                 : 2.0f;
-    const uint32_t ngroups = phich_mi * (uint32_t)ceilf(ng * ((float)cell.nof_prb / 8));
+    const uint32_t    ngroups = phich_ngroups(cell, phich_mi);
     std::vector<Reg*> free_l[3];
     for (auto& r : regs)
       if (r.l < 3 && !r.taken) free_l[r.l].push_back(&r);
@@ -438,9 +445,18 @@ BlindJob blind_plan(const mi355_cell_t& cell, uint32_t sf_idx, uint16_t rnti, co
 
 // dci_blind_search (ue_dl.c:450-550) per search space, as find_dl_dci_type_* call it (ue_dl.c:644-692)
 int blind_search_replay(const mi355_cell_t& cell, uint32_t nof_cce, uint16_t rnti, const mi355_ue_dl_cfg_t& cfg,
-                        const BlindJob& j, const DciCand* cand, mi355_dci_msg_t* msgs)
+                        const BlindJob& j, const DciCand* cand, mi355_dci_msg_t* msgs, mi355_dci_msg_t* ul_msgs,
+                        uint32_t* nof_ul)
 {
   if (!rnti) return 0;
+  // find_dci (ue_dl.c:420-434)
+  auto find_dci = [](const mi355_dci_msg_t* list, uint32_t n, const mi355_dci_msg_t& m) {
+    for (uint32_t q = 0; q < n; q++)
+      if (list[q].nof_bits == m.nof_bits && memcmp(list[q].payload, m.payload, m.nof_bits) == 0) return true;
+    return false;
+  };
+  uint32_t  none    = 0; // no list given: nothing is pending, nothing is kept
+  uint32_t& pending = ul_msgs && nof_ul ? *nof_ul : none;
   std::vector<mi355_dci_location_t> allocated;
   int                               total = 0;
   mi355_dci_location_t              com[MI355_MAX_CANDIDATES_COM];
@@ -479,13 +495,14 @@ int blind_search_replay(const mi355_cell_t& cell, uint32_t nof_cce, uint16_t rnt
           if (on_common && m.nof_bits == dci_size(cell, cc, MI355_DCI_FORMAT1A))
             m.format = m.payload[0] ? MI355_DCI_FORMAT1A : MI355_DCI_FORMAT0;
         }
-        if (m.format == MI355_DCI_FORMAT0) continue; // kept for srslte_ue_dl_find_ul_dci, not a DL grant
-        bool dup = false;
-        for (int q = 0; q < found && !dup; q++) {
-          const mi355_dci_msg_t& o = msgs[total + q];
-          dup = o.nof_bits == m.nof_bits && memcmp(o.payload, m.payload, m.nof_bits) == 0;
+        if (m.format == MI355_DCI_FORMAT0) {
+          // kept for srslte_ue_dl_find_ul_dci (ue_dl.c:521-529), not a DL grant: stored once however often it is
+          // seen, its location stays free and the format loop goes on
+          if (ul_msgs && pending < MI355_MAX_DCI_MSG && !find_dci(ul_msgs, pending, m)) ul_msgs[pending++] = m;
+          continue;
         }
-        if (dup) continue;
+        // duplicates of this search's messages and of the pending UL ones are ignored (ue_dl.c:531-532)
+        if (find_dci(&msgs[total], (uint32_t)found, m) || find_dci(ul_msgs, pending, m)) continue;
         allocated.push_back(m.location);
         found++;
         break;
@@ -1089,6 +1106,136 @@ int mi355_pbch_encode_host(const mi355_cell_t* cell, const uint8_t* bch_payload,
   const std::vector<uint32_t> re = pbch_re(*cell);
   for (uint32_t p = 0; p < cell->nof_ports; p++)
     for (uint32_t i = 0; i < MI355_PBCH_NOF_RE; i++) reinterpret_cast<float2*>(sf_symbols[p])[re[i]] = y[p][i];
+  return MI355_SUCCESS;
+}
+
+// ---------------------------------------------------------------------------------------- PHICH, UL grants (phich.h)
+
+uint32_t mi355_phich_ngroups(const mi355_cell_t* cell) { return cell ? phich_ngroups(*cell, 1) : 0; }
+
+int mi355_phich_calc(const mi355_cell_t* cell, const mi355_phich_grant_t* grant, mi355_phich_resource_t* n_phich)
+{
+  if (!cell || !grant || !n_phich) return MI355_ERROR_INVALID_INPUTS;
+  const uint32_t Ngroups = phich_ngroups(*cell, 1); // srslte_regs_phich_ngroups_m1
+  if (!Ngroups) return MI355_ERROR;                 // "Ngroups is zero"
+  n_phich->ngroup = (grant->n_prb_lowest + grant->n_dmrs) % Ngroups + grant->I_phich * Ngroups;
+  n_phich->nseq   = ((grant->n_prb_lowest / Ngroups) + grant->n_dmrs) % (2 * MI355_PHICH_NORM_NSF);
+  return MI355_SUCCESS;
+}
+
+int mi355_phich_encode_host(const mi355_cell_t* cell, const mi355_dl_sf_cfg_t* sf, mi355_phich_resource_t n_phich,
+                            uint8_t ack, float* const* sf_symbols)
+{
+  RegMap m;
+  if (!cell || !sf || !sf_symbols || cell->cp != MI355_CP_NORM || n_phich.nseq >= MI355_PHICH_NORM_NSEQUENCES ||
+      !(cell->nof_ports == 1 || cell->nof_ports == 2 || cell->nof_ports == 4) || !regs_build(*cell, 1, m) ||
+      (size_t)(n_phich.ngroup + 1) * MI355_PHICH_MAX_NSYMB > m.phich.size())
+    return MI355_ERROR_INVALID_INPUTS;
+  for (uint32_t p = 0; p < cell->nof_ports; p++)
+    if (!sf_symbols[p]) return MI355_ERROR_INVALID_INPUTS;
+  // the ACK bit three times (srslte_phich_ack_encode), BPSK (0 -> (1 + j) / sqrt2), spreading with w_normal[nseq]
+  // (36.211 Table 6.9.1-2: +-1 for nseq < 4, +-j above), the +-1 scrambling sequence (sequences.c:45-48)
+  static const int8_t w[4][4] = {{1, 1, 1, 1}, {1, -1, 1, -1}, {1, 1, -1, -1}, {1, -1, -1, 1}};
+  std::vector<uint8_t> c;
+  gold_sequence((sf->tti % 10 + 1) * (2 * cell->id + 1) * 512 + cell->id, MI355_PHICH_MAX_NSYMB, c);
+  const float         s = (float)M_SQRT1_2, zr = ack ? -s : s, zi = ack ? -s : s;
+  std::vector<float2> d(MI355_PHICH_MAX_NSYMB);
+  for (uint32_t i = 0; i < MI355_PHICH_MAX_NSYMB; i++) {
+    const float sg = (float)w[n_phich.nseq % 4][i % 4] * (c[i] ? -1.f : 1.f);
+    d[i]           = n_phich.nseq < 4 ? make_float2(sg * zr, sg * zi) : make_float2(-sg * zi, sg * zr); // j z = -zi + j zr
+  }
+  std::vector<float2> y[MI355_MAX_PORTS];
+  precode_diversity(d, cell->nof_ports, y);
+  const uint32_t* re = &m.phich[(size_t)n_phich.ngroup * MI355_PHICH_MAX_NSYMB];
+  for (uint32_t p = 0; p < cell->nof_ports; p++) {
+    float2* g = reinterpret_cast<float2*>(sf_symbols[p]);
+    for (uint32_t i = 0; i < MI355_PHICH_MAX_NSYMB; i++) g[re[i]].x += y[p][i].x, g[re[i]].y += y[p][i].y; // regs_add_reg
+  }
+  return MI355_SUCCESS;
+}
+
+// dci_format0_unpack (dci.c:494-574), FDD
+int mi355_dci_msg_unpack_pusch(const mi355_cell_t* cell, const mi355_dl_sf_cfg_t* sf, const mi355_dci_cfg_t* cfg_,
+                               mi355_dci_msg_t* msg, mi355_dci_ul_t* dci)
+{
+  (void)sf;
+  if (!cell || !msg || !dci) return MI355_ERROR_INVALID_INPUTS;
+  mi355_dci_cfg_t cfg{};
+  if (cfg_) cfg = *cfg_;
+  memset(dci, 0, sizeof(*dci));
+  dci->rnti     = msg->rnti;
+  dci->location = msg->location;
+  dci->format   = msg->format;
+  BitReader y{msg->payload};
+  if (cfg.cif_enabled) {
+    dci->cif         = y.take(3);
+    dci->cif_present = 1;
+  }
+  if (y.bit() != 0) return MI355_ERROR; // "DCI message is Format1A"
+  msg->format = MI355_DCI_FORMAT0;
+  uint32_t n_ul_hop = 0;
+  if (y.bit() == 0) {
+    dci->freq_hop_fl = MI355_RA_PUSCH_HOP_DISABLED;
+  } else {
+    n_ul_hop         = cell->nof_prb < 50 ? 1 : 2; // 36.213 Table 8.4-1
+    dci->freq_hop_fl = (int32_t)y.take(n_ul_hop);
+  }
+  dci->type2_alloc.riv = y.take(riv_nbits(cell->nof_prb) - n_ul_hop);
+  dci->tb.mcs_idx      = y.take(5);
+  dci->tb.ndi          = y.bit();
+  dci->tpc_pusch       = (uint8_t)y.take(2);
+  dci->n_dmrs          = y.take(3);
+  if (cfg.multiple_csi_request_enabled && !cfg.is_not_ue_ss) {
+    dci->multiple_csi_request_present = 1;
+    dci->multiple_csi_request         = (uint8_t)y.take(2);
+  } else {
+    dci->cqi_request = y.bit();
+  }
+  if (cfg.srs_request_enabled && !cfg.is_not_ue_ss) {
+    dci->srs_request_present = 1;
+    dci->srs_request         = y.bit();
+  }
+  if (cfg.ra_format_enabled) {
+    dci->ra_type_present = 1;
+    dci->ra_type         = y.bit();
+  }
+  return MI355_SUCCESS;
+}
+
+// dci_format0_pack (dci.c:416-487), FDD
+int mi355_dci_msg_pack_pusch(const mi355_cell_t* cell, const mi355_dl_sf_cfg_t* sf, const mi355_dci_cfg_t* cfg_,
+                             const mi355_dci_ul_t* dci, mi355_dci_msg_t* msg)
+{
+  (void)sf;
+  if (!cell || !msg || !dci) return MI355_ERROR_INVALID_INPUTS;
+  mi355_dci_cfg_t cfg{};
+  if (cfg_) cfg = *cfg_;
+  memset(msg, 0, sizeof(*msg));
+  msg->rnti     = dci->rnti;
+  msg->location = dci->location;
+  msg->format   = dci->format;
+  BitWriter y{msg->payload};
+  if (dci->cif_present) y.put(dci->cif, 3);
+  y.put(0, 1); // format differentiation
+  uint32_t n_ul_hop = 0;
+  if (dci->freq_hop_fl == MI355_RA_PUSCH_HOP_DISABLED) {
+    y.put(0, 1);
+  } else {
+    y.put(1, 1);
+    n_ul_hop = cell->nof_prb < 50 ? 1 : 2;
+    y.put((uint32_t)dci->freq_hop_fl, n_ul_hop);
+  }
+  y.put(dci->type2_alloc.riv, riv_nbits(cell->nof_prb) - n_ul_hop);
+  y.put(dci->tb.mcs_idx, 5);
+  y.put(dci->tb.ndi, 1);
+  y.put(dci->tpc_pusch, 2);
+  y.put(dci->n_dmrs, 3);
+  y.put(dci->cqi_request, 1);
+  if (cfg.multiple_csi_request_enabled && !cfg.is_not_ue_ss) y.put(0, 1);
+  if (cfg.srs_request_enabled && !cfg.is_not_ue_ss) y.put(dci->srs_request && dci->srs_request_present ? 1 : 0, 1);
+  const uint32_t n = dci_size(*cell, cfg, MI355_DCI_FORMAT0);
+  while ((uint32_t)(y.p - msg->payload) < n) *y.p++ = 0;
+  msg->nof_bits = (uint32_t)(y.p - msg->payload);
   return MI355_SUCCESS;
 }
 

@@ -23,6 +23,8 @@ struct RegMap {
   std::vector<uint32_t> phich;    // 12 REs per group
 };
 bool regs_build(const mi355_cell_t& cell, uint32_t phich_mi, RegMap& m);
+// PHICH groups of the cell (srslte_regs_phich_ngroups): phich_mi * ceil(Ng * nof_prb / 8), what regs_build lays out
+uint32_t phich_ngroups(const mi355_cell_t& cell, uint32_t phich_mi);
 
 // One subframe of the control-channel stage (device pointers)
 struct CtrlJob {
@@ -114,15 +116,40 @@ struct ConvDebugJob {
 hipError_t ctrl_launch_conv_debug(const ConvDebugJob* jobs, const float* llr, DciCand* out, uint32_t njobs,
                                   hipStream_t s);
 
+// PHICH decoding (phich_kernels.hip): 4 lanes per job, lanes 0..2 one REG (one ACK bit) each
+struct PhichJob {
+  uint32_t sf;     // index into PhichArgs::sfs
+  uint32_t ngroup; // < ngroups (checked on the host)
+  uint32_t nseq;   // < 8
+};
+struct PhichOut {
+  uint32_t ack;
+  float    distance;
+};
+struct PhichArgs {
+  const CtrlJob*  sfs;  // the subframes the jobs name (grids, estimates, noise, sf_idx)
+  const PhichJob* jobs;
+  const uint32_t* re;   // [ngroups][12] grid indices
+  const uint32_t* seq;  // [10]: 12 scrambling bits per subframe index, bit j = c(j)
+  uint32_t        njobs;
+  uint32_t        nof_rx, nof_ports;
+  uint32_t        ce_row; // as CtrlArgs::ce_row
+  PhichOut*       out;    // [njobs]
+};
+hipError_t phich_launch_decode(const PhichArgs& a, hipStream_t s);
+
 // host search-space generation (pdcch.c:222-330), shared by the runtime's blind-search replay
 uint32_t ue_locations(uint32_t nof_cce, uint32_t Yk, mi355_dci_location_t* c);
 uint32_t common_locations(uint32_t nof_cce, mi355_dci_location_t* c);
 uint32_t ue_search_hash(uint16_t rnti, uint32_t sf_idx);
 
 // The reference's sequential blind search (ue_dl.c:450-730) over the decoded candidates of one subframe:
-// fills msgs (<= MI355_MAX_DCI_MSG) and returns their number.
+// fills msgs (<= MI355_MAX_DCI_MSG) and returns their number.  The format-0 messages it comes across are appended to
+// ul_msgs (<= MI355_MAX_DCI_MSG, *nof_ul their count on entry and on return) by the pending-UL rules of
+// ue_dl.c:521-532; ul_msgs == nullptr: dropped.
 int blind_search_replay(const mi355_cell_t& cell, uint32_t nof_cce, uint16_t rnti, const mi355_ue_dl_cfg_t& cfg,
-                        const BlindJob& plan, const DciCand* cand, mi355_dci_msg_t* msgs);
+                        const BlindJob& plan, const DciCand* cand, mi355_dci_msg_t* msgs,
+                        mi355_dci_msg_t* ul_msgs = nullptr, uint32_t* nof_ul = nullptr);
 // per-job search plan (spaces, payload sizes) for the device
 BlindJob blind_plan(const mi355_cell_t& cell, uint32_t sf_idx, uint16_t rnti, const mi355_ue_dl_cfg_t& cfg);
 

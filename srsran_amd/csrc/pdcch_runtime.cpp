@@ -1,7 +1,8 @@
 // srsran_amd/csrc/pdcch_runtime.cpp -- host runtime of the control-channel stage: the cell's REG map and
 // scrambling sequences resident in HBM, per-call descriptor upload, the two kernels (PCFICH + PDCCH LLRs, blind
 // candidate decoding), one read-back of the CFIs and candidate results, and the host replay of the UE's
-// sequential blind search (ue_dl.c:450-730).
+// sequential blind search (ue_dl.c:450-730), which also sets the UL grants (format 0) aside; and the PHICH call:
+// (subframe, resource) records up, one phich_decode launch, 8 bytes per job back.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,6 +29,8 @@ CtrlState::~CtrlState()
   if (rb) (void)hipStreamDestroy(rb);
   delete st;
   delete back;
+  delete pst;
+  delete pback;
 }
 
 int CtrlState::init(const mi355_cell_t& c, uint32_t nrx)
@@ -51,9 +54,71 @@ int CtrlState::init(const mi355_cell_t& c, uint32_t nrx)
     for (uint32_t j = 0; j < 32 * seq_words; j++)
       tab[16 + 3 * PDCCH_MAX_REGS * 4 + 10 + sf * seq_words + j / 32] |= (uint32_t)c0[j] << (j % 32);
   }
+  // ... | phich_re[ngroups][12] | phich_seq[10] (12 scrambling bits per subframe index, sequences.c:45-48: the
+  // PCFICH's c_init, nslot = 2 sf)
+  ngroups   = (uint32_t)regs.phich.size() / 12;
+  phich_tab = (uint32_t)tab.size();
+  tab.insert(tab.end(), regs.phich.begin(), regs.phich.end());
+  for (uint32_t sf = 0; sf < 10; sf++) {
+    gold_sequence((sf + 1) * (2 * cell.id + 1) * 512 + cell.id, 12, c0);
+    uint32_t w = 0;
+    for (uint32_t j = 0; j < 12; j++) w |= (uint32_t)c0[j] << j;
+    tab.push_back(w);
+  }
   CHECK_HIP(d_tab.upload(tab));
-  st   = new HostStaging;
-  back = new HostStaging;
+  st    = new HostStaging;
+  back  = new HostStaging;
+  pst   = new HostStaging;
+  pback = new HostStaging;
+  return MI355_SUCCESS;
+}
+
+int CtrlState::phich(const mi355_dl_sf_job_t* sfjobs, const mi355_dl_sf_cfg_t* sfs, const mi355_chest_dl_res_t* chest,
+                     uint32_t nsf, const PhichJob* jobs, uint32_t njobs, uint32_t ce_row_phich, hipStream_t s,
+                     PhichOut* out)
+{
+  if (!njobs) return MI355_SUCCESS;
+  const size_t b_sf = staged_size((size_t)nsf * sizeof(CtrlJob)), b_jobs = staged_size((size_t)njobs * sizeof(PhichJob));
+  const size_t b_out = staged_size((size_t)njobs * sizeof(PhichOut)), need = b_sf + b_jobs + b_out;
+  CHECK_HIP(d_phich.reserve(need, need + need / 4, DevScratch::SyncFree));
+  char* base = d_phich.base();
+  CHECK_HIP(pst->reserve(b_sf + b_jobs));
+  auto* cj = (CtrlJob*)pst->slot((size_t)nsf * sizeof(CtrlJob));
+  auto* pj = (PhichJob*)pst->slot((size_t)njobs * sizeof(PhichJob));
+  memset(cj, 0, (size_t)nsf * sizeof(CtrlJob));
+  std::vector<uint8_t> named(nsf, 0);
+  for (uint32_t i = 0; i < njobs; i++) named[jobs[i].sf] = 1;
+  for (uint32_t i = 0; i < nsf; i++) {
+    if (!named[i]) continue; // never read on the device
+    CtrlJob& J = cj[i];
+    for (uint32_t r = 0; r < nof_rx; r++) {
+      if (!sfjobs[i].sf_symbols[r]) return MI355_ERROR_INVALID_INPUTS;
+      J.grid[r] = (const float2*)sfjobs[i].sf_symbols[r];
+      for (uint32_t p = 0; p < cell.nof_ports; p++) {
+        if (!sfjobs[i].ce[p][r]) return MI355_ERROR_INVALID_INPUTS;
+        J.ce[p][r] = (const float2*)sfjobs[i].ce[p][r];
+      }
+    }
+    J.noise  = chest[i].noise_estimate;
+    J.sf_idx = sfs[i].tti % 10;
+  }
+  memcpy(pj, jobs, (size_t)njobs * sizeof(PhichJob));
+  CHECK_HIP(pst->upload(base, s));
+  PhichArgs a{};
+  a.sfs       = (const CtrlJob*)base;
+  a.jobs      = (const PhichJob*)(base + b_sf);
+  a.re        = d_tab.as<uint32_t>() + phich_tab;
+  a.seq       = a.re + (size_t)ngroups * 12;
+  a.njobs     = njobs;
+  a.nof_rx    = nof_rx;
+  a.nof_ports = cell.nof_ports;
+  a.ce_row    = ce_row_phich;
+  a.out       = (PhichOut*)(base + b_sf + b_jobs);
+  CHECK_HIP(phich_launch_decode(a, s));
+  CHECK_HIP(pback->reserve((size_t)njobs * sizeof(PhichOut)));
+  CHECK_HIP(stage_copy(pback->host, a.out, (size_t)njobs * sizeof(PhichOut), s));
+  CHECK_HIP(wait_stream(s));
+  memcpy(out, pback->host, (size_t)njobs * sizeof(PhichOut));
   return MI355_SUCCESS;
 }
 
@@ -82,6 +147,10 @@ int CtrlState::launch(const mi355_dl_sf_job_t* sfjobs, const float* host_noise, 
   CHECK_HIP(d_buf.reserve(need, need + need / 4, DevScratch::SyncFree));
   char* base = d_buf.base();
   plan_of.resize(n);
+  // every control-stage call starts each subframe's pending UL list empty (the messages' slots are written before
+  // they are counted: grown, never cleared)
+  ul_cnt.assign(n, 0u);
+  if (ul_msgs.size() < (size_t)n * MI355_MAX_DCI_MSG) ul_msgs.resize((size_t)n * MI355_MAX_DCI_MSG);
   CHECK_HIP(st->reserve(b_jobs + b_blind));
   auto* cj = (CtrlJob*)st->slot((size_t)n * sizeof(CtrlJob));
   auto* bj = (BlindJob*)st->slot((size_t)n * sizeof(BlindJob));
@@ -242,7 +311,8 @@ int CtrlState::finish(uint32_t chunk, const uint16_t* rntis, const mi355_ue_dl_c
         }
       }
       res[i].nof_dci = blind_search_replay(cell, res[i].nof_cce, rntis[i], cfgs[i], plan_of[i], cand,
-                                           msgs + (size_t)i * MI355_MAX_DCI_MSG);
+                                           msgs + (size_t)i * MI355_MAX_DCI_MSG,
+                                           ul_msgs.data() + (size_t)i * MI355_MAX_DCI_MSG, &ul_cnt[i]);
     }
   });
   if (prof)

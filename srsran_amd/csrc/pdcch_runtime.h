@@ -28,6 +28,14 @@ struct CtrlState {
   std::unordered_map<uint64_t, BlindJob> plans; // search plan per (rnti, subframe, UE configuration)
   std::vector<BlindJob>                  plan_of; // this call's plan per subframe
   uint32_t                               ce_row = 0; // set by the caller: estimates time-invariant, read row 0
+  // the format-0 messages the previous call's replay kept per subframe (ue_dl.c:521-529), drained by mi355_ue_dl_find_ul_dci_batch
+  std::vector<mi355_dci_msg_t> ul_msgs; // [n][MI355_MAX_DCI_MSG]
+  std::vector<uint32_t>        ul_cnt;  // [n], every launch() starts them at 0
+  // PHICH: phich_re[ngroups][12] | phich_seq[10] behind the PDCCH words in d_tab; a call's arena and stagings
+  uint32_t     phich_tab = 0, ngroups = 0;
+  DevScratch   d_phich;
+  HostStaging* pst   = nullptr;
+  HostStaging* pback = nullptr;
 
   // launch(): the arena layout and the per-chunk completion events of the pending call
   size_t                b_cfi_ = 0, b_corr_ = 0;
@@ -52,6 +60,11 @@ struct CtrlState {
              const std::function<int(uint32_t, uint32_t)>& front = nullptr);
   int finish(uint32_t chunk, const uint16_t* rntis, const mi355_ue_dl_cfg_t* cfgs, mi355_ctrl_res_t* res,
              mi355_dci_msg_t* msgs);
+  // srslte_phich_decode for njobs (subframe, resource) pairs on s, synchronous: out[i] for every job.  The caller has
+  // checked sf < nsf and ngroup < ngroups, nseq < 8 for every job.  Subframe i: grids / estimates of sfjobs[i],
+  // scrambling of sfs[i].tti % 10, noise chest[i].noise_estimate.
+  int phich(const mi355_dl_sf_job_t* sfjobs, const mi355_dl_sf_cfg_t* sfs, const mi355_chest_dl_res_t* chest,
+            uint32_t nsf, const PhichJob* jobs, uint32_t njobs, uint32_t ce_row_phich, hipStream_t s, PhichOut* out);
 };
 
 } // namespace mi355

@@ -15,6 +15,7 @@
 
 #include "../../include/srsran_amd/pdcch.h"
 #include "../../include/srsran_amd/pdsch.h"
+#include "../../include/srsran_amd/phich.h"
 #include "../../include/srsran_amd/tdec.h"
 #include "../../include/srsran_amd/ue_dl.h"
 #include "device_mem.h"
@@ -985,6 +986,64 @@ int mi355_ue_dl_find_and_decode_batch(mi355_ue_dl_t* q, mi355_softbuffer_pool_t*
             us(t0, t1), us(t1, t1c), us(t2a, t2), us(t2, t3));
   }
   return r;
+}
+
+// srslte_ue_dl_find_ul_dci (ue_dl.c:613-641) over the lists the previous control-stage call's replay kept
+int mi355_ue_dl_find_ul_dci_batch(mi355_ue_dl_t* q, const mi355_dl_sf_cfg_t* sfs, const mi355_ue_dl_cfg_t* cfgs,
+                                  const uint16_t* rntis, uint32_t njobs, int32_t* nof_ul, mi355_dci_ul_t* dci_ul)
+{
+  if (!q || (njobs && (!sfs || !cfgs || !rntis || !nof_ul || !dci_ul))) return MI355_ERROR_INVALID_INPUTS;
+  std::lock_guard<std::mutex> lock(q->mu);
+  if (!njobs) return MI355_SUCCESS;
+  if (!q->ctrl || njobs > q->ctrl->ul_cnt.size()) return MI355_ERROR_INVALID_INPUTS;
+  for (uint32_t i = 0; i < njobs; i++) {
+    nof_ul[i] = 0;
+    if (!rntis[i]) continue; // (the list stays, as in the reference)
+    const uint32_t n     = std::min<uint32_t>(MI355_MAX_DCI_MSG, q->ctrl->ul_cnt[i]);
+    q->ctrl->ul_cnt[i]   = 0;
+    mi355_dci_msg_t* pen = q->ctrl->ul_msgs.data() + (size_t)i * MI355_MAX_DCI_MSG;
+    nof_ul[i]            = (int32_t)n;
+    for (uint32_t k = 0; k < n; k++)
+      if (mi355_dci_msg_unpack_pusch(&q->cell, &sfs[i], &cfgs[i].dci, &pen[k], &dci_ul[(size_t)i * MI355_MAX_DCI_MSG + k])) {
+        nof_ul[i] = -1; // "Unpacking UL DCI"
+        break;
+      }
+  }
+  return MI355_SUCCESS;
+}
+
+// srslte_ue_dl_decode_phich (ue_dl.c:757-790) per job; jobs the reference's srslte_phich_decode refuses
+// (phich.c:217-220) are answered on the host
+int mi355_ue_dl_decode_phich_batch(mi355_ue_dl_t* q, const mi355_dl_sf_job_t* sfjobs, const mi355_dl_sf_cfg_t* sfs,
+                                   const mi355_chest_dl_res_t* chest, uint32_t nsf, const mi355_phich_job_t* jobs,
+                                   uint32_t njobs, mi355_phich_res_t* res, void* stream)
+{
+  if (!q || (njobs && (!jobs || !res)) || (njobs && nsf && (!sfjobs || !sfs || !chest))) return MI355_ERROR_INVALID_INPUTS;
+  if (!njobs) return MI355_SUCCESS;
+  if (q->cell.cp != MI355_CP_NORM) return MI355_ERROR_INVALID_INPUTS;
+  std::lock_guard<std::mutex> lock(q->mu);
+  CHECK_HIP(hipSetDevice(q->device));
+  int r = ctrl_ready(q);
+  if (r) return r;
+  std::vector<PhichJob> dev;
+  std::vector<uint32_t> which;
+  dev.reserve(njobs), which.reserve(njobs);
+  for (uint32_t i = 0; i < njobs; i++) {
+    res[i] = mi355_phich_res_t{MI355_ERROR_INVALID_INPUTS, 0u, 0.f};
+    mi355_phich_resource_t n{};
+    if (jobs[i].sf >= nsf || mi355_phich_calc(&q->cell, &jobs[i].grant, &n) || n.ngroup >= q->ctrl->ngroups) continue;
+    dev.push_back(PhichJob{jobs[i].sf, n.ngroup, n.nseq});
+    which.push_back(i);
+  }
+  if (dev.empty()) return MI355_SUCCESS;
+  std::vector<PhichOut> out(dev.size());
+  // estimates written by the batched decode calls under set_ce_rows(1) have row 0 only
+  const uint32_t ce_row = q->ce_rows == 1 ? 12 * q->cell.nof_prb : 0u;
+  if ((r = q->ctrl->phich(sfjobs, sfs, chest, nsf, dev.data(), (uint32_t)dev.size(), ce_row,
+                          stream ? (hipStream_t)stream : q->own, out.data())))
+    return r;
+  for (size_t k = 0; k < dev.size(); k++) res[which[k]] = mi355_phich_res_t{MI355_SUCCESS, out[k].ack, out[k].distance};
+  return MI355_SUCCESS;
 }
 
 int mi355_ue_dl_ctrl_llr(mi355_ue_dl_t* q, uint32_t i, float* llr, uint32_t max_llr)
