@@ -13,58 +13,11 @@
 #include <stdint.h>
 
 #include "tdec_internal.h"
+#include "tdec_trellis.h"
 
 namespace mi355 {
 
-typedef short v2s __attribute__((ext_vector_type(2)));
-
 namespace {
-__device__ __forceinline__ v2s U(uint32_t u) { return __builtin_bit_cast(v2s, u); }
-__device__ __forceinline__ uint32_t W(v2s v) { return __builtin_bit_cast(uint32_t, v); }
-__device__ __forceinline__ v2s vmax(v2s a, v2s b) { return __builtin_elementwise_max(a, b); }
-__device__ __forceinline__ v2s splat(short s) { return (v2s){s, s}; }
-
-__device__ __forceinline__ void gbeta(const v2s o[8], v2s x, v2s y, v2s n[8])
-{
-  v2s xy = x + y;
-  n[0]   = vmax(o[4] + xy, o[0]);
-  n[1]   = vmax(o[4], o[0] + xy);
-  n[2]   = vmax(o[5] + y, o[1] + x);
-  n[3]   = vmax(o[5] + x, o[1] + y);
-  n[4]   = vmax(o[6] + x, o[2] + y);
-  n[5]   = vmax(o[6] + y, o[2] + x);
-  n[6]   = vmax(o[7], o[3] + xy);
-  n[7]   = vmax(o[7] + xy, o[3]);
-}
-
-__device__ __forceinline__ void galpha(const v2s o[8], v2s x, v2s y, v2s c0[8], v2s c1[8])
-{
-  v2s xy = x + y;
-  c0[0]  = o[0];
-  c1[0]  = o[1] + xy;
-  c0[1]  = o[3] + y;
-  c1[1]  = o[2] + x;
-  c0[2]  = o[4] + y;
-  c1[2]  = o[5] + x;
-  c0[3]  = o[7];
-  c1[3]  = o[6] + xy;
-  c0[4]  = o[1];
-  c1[4]  = o[0] + xy;
-  c0[5]  = o[2] + y;
-  c1[5]  = o[3] + x;
-  c0[6]  = o[5] + y;
-  c1[6]  = o[4] + x;
-  c0[7]  = o[6];
-  c1[7]  = o[7] + xy;
-}
-
-__device__ __forceinline__ void gnorm(v2s s[8])
-{
-#pragma unroll
-  for (int i = 1; i < 8; i++) s[i] = s[i] - s[0];
-  s[0] = splat(0);
-}
-
 __device__ __forceinline__ void store_row(uint32_t* c, const v2s s[8])
 {
   uint4* c4 = (uint4*)c;
@@ -97,7 +50,7 @@ __global__ __launch_bounds__(256) void tdec_gen_halfit(TdecGenArgs a)
   for (int k = K + 2; k >= 0; k--) {
     v2s x = U(X[k]);
     if (has_ap && k < K) x = x + U(A[k]);
-    gbeta(st, x, U(Y[k]), nw);
+    beta_step<false>(st, x, U(Y[k]), nw);
 #pragma unroll
     for (int i = 0; i < 8; i++) st[i] = nw[i];
     if (k == K) {
@@ -105,7 +58,7 @@ __global__ __launch_bounds__(256) void tdec_gen_halfit(TdecGenArgs a)
     } else if (k < K && k > 0 && k % SEG == 0) {
       store_row(ck + (size_t)(k / SEG - 1) * 8, st);
     }
-    if ((k & 3) == 0 && k < K) gnorm(st);
+    if ((k & 3) == 0 && k < K) normalize<false>(st);
   }
 
   // ------------------------------------------------ forward pass (turbodecoder_gen.c:114-198)
@@ -153,12 +106,12 @@ __global__ __launch_bounds__(256) void tdec_gen_halfit(TdecGenArgs a)
         }
 #pragma unroll
         for (int s = 0; s < 8; s++) cur[s] = rows[i][s];
-        if ((j & 3) == 0 && j < K) gnorm(cur);
+        if ((j & 3) == 0 && j < K) normalize<false>(cur);
       } else if (j < e) {
-        gbeta(cur, xin[i], yin[i], rows[i]);
+        beta_step<false>(cur, xin[i], yin[i], rows[i]);
 #pragma unroll
         for (int s = 0; s < 8; s++) cur[s] = rows[i][s];
-        if ((j & 3) == 0) gnorm(cur);
+        if ((j & 3) == 0) normalize<false>(cur);
       }
     }
 #pragma unroll
@@ -166,7 +119,7 @@ __global__ __launch_bounds__(256) void tdec_gen_halfit(TdecGenArgs a)
       const int k = s0 + i + 1; // 1-based alpha step, input k-1 = s0+i, beta row k = rows[i+1]
       if (k <= e) {
         v2s c0[8], c1[8];
-        galpha(st, xin[i], yin[i], c0, c1);
+        alpha_cands<false>(st, xin[i], yin[i], c0, c1);
         v2s m0 = c0[0] + rows[i + 1][0];
         v2s m1 = c1[0] + rows[i + 1][0];
 #pragma unroll
@@ -176,7 +129,7 @@ __global__ __launch_bounds__(256) void tdec_gen_halfit(TdecGenArgs a)
         }
 #pragma unroll
         for (int s = 0; s < 8; s++) st[s] = vmax(c0[s], c1[s]);
-        if ((k & 3) == 0) gnorm(st);
+        if ((k & 3) == 0) normalize<false>(st);
         const v2s out = m1 - m0;
         const int pos = k - 1;
         if (!dec2) {

@@ -33,17 +33,10 @@
 
 #include "crc_device.h"
 #include "tdec_internal.h"
+#include "tdec_trellis.h"
 
 namespace mi355 {
 
-typedef short v2s __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ v2s U(uint32_t u) { return __builtin_bit_cast(v2s, u); }
-__device__ __forceinline__ uint32_t W(v2s v) { return __builtin_bit_cast(uint32_t, v); }
-__device__ __forceinline__ v2s sadd(v2s a, v2s b) { return __builtin_elementwise_add_sat(a, b); }
-__device__ __forceinline__ v2s ssub(v2s a, v2s b) { return __builtin_elementwise_sub_sat(a, b); }
-__device__ __forceinline__ v2s vmax(v2s a, v2s b) { return __builtin_elementwise_max(a, b); }
-__device__ __forceinline__ v2s splat(short s) { return (v2s){s, s}; }
 // (a.hi, b.lo): the pair "second window of this lane, first window of the next lane"
 __device__ __forceinline__ uint32_t hi_lo(uint32_t a, uint32_t b) { return __builtin_amdgcn_alignbit(b, a, 16); }
 // the word lane q-1 / q+1 holds (DPP row_shr:1 / row_shl:1 inside 16-lane rows; a code block's NL <= 8 lanes never
@@ -63,75 +56,6 @@ __device__ __forceinline__ void bm_set(uint32_t* bm, uint32_t m, bool v)
 {
   const uint32_t by = m >> 3;
   if (v) atomicOr(&bm[by >> 2], 1u << (((by & 3) << 3) + 7 - (m & 7)));
-}
-
-// ---------------------------------------------------------------------------- trellis steps
-// State numbering reg0<<2|reg1<<1|reg2, branch metric u*x + p*y (turbocoder.c:403-421).
-
-template <bool SAT>
-__device__ __forceinline__ v2s add(v2s a, v2s b)
-{
-  if constexpr (SAT) {
-    return sadd(a, b);
-  } else {
-    return a + b;
-  }
-}
-
-template <bool SAT>
-__device__ __forceinline__ void beta_step(const v2s o[8], v2s x, v2s y, v2s n[8])
-{
-  v2s xy = add<SAT>(x, y);
-  n[0]   = vmax(add<SAT>(o[4], xy), o[0]);
-  n[1]   = vmax(o[4], add<SAT>(o[0], xy));
-  n[2]   = vmax(add<SAT>(o[5], y), add<SAT>(o[1], x));
-  n[3]   = vmax(add<SAT>(o[5], x), add<SAT>(o[1], y));
-  n[4]   = vmax(add<SAT>(o[6], x), add<SAT>(o[2], y));
-  n[5]   = vmax(add<SAT>(o[6], y), add<SAT>(o[2], x));
-  n[6]   = vmax(o[7], add<SAT>(o[3], xy));
-  n[7]   = vmax(add<SAT>(o[7], xy), o[3]);
-}
-
-template <bool SAT>
-__device__ __forceinline__ void alpha_cands(const v2s o[8], v2s x, v2s y, v2s c0[8], v2s c1[8])
-{
-  v2s xy = add<SAT>(x, y);
-  c0[0]  = o[0];
-  c1[0]  = add<SAT>(o[1], xy);
-  c0[1]  = add<SAT>(o[3], y);
-  c1[1]  = add<SAT>(o[2], x);
-  c0[2]  = add<SAT>(o[4], y);
-  c1[2]  = add<SAT>(o[5], x);
-  c0[3]  = o[7];
-  c1[3]  = add<SAT>(o[6], xy);
-  c0[4]  = o[1];
-  c1[4]  = add<SAT>(o[0], xy);
-  c0[5]  = add<SAT>(o[2], y);
-  c1[5]  = add<SAT>(o[3], x);
-  c0[6]  = add<SAT>(o[5], y);
-  c1[6]  = add<SAT>(o[4], x);
-  c0[7]  = o[6];
-  c1[7]  = add<SAT>(o[7], xy);
-}
-
-template <bool SAT>
-__device__ __forceinline__ void normalize(v2s s[8])
-{
-#pragma unroll
-  for (int i = 1; i < 8; i++) {
-    if constexpr (SAT) {
-      s[i] = ssub(s[i], s[0]);
-    } else {
-      s[i] = s[i] - s[0];
-    }
-  }
-  s[0] = splat(0);
-}
-
-__device__ __forceinline__ void set_minf(v2s s[8])
-{
-#pragma unroll
-  for (int i = 0; i < 8; i++) s[i] = splat(-TDEC_INF);
 }
 
 // ---------------------------------------------------------------------------- fused code-block check
@@ -211,72 +135,22 @@ __shared__ uint32_t tdec_stg_row[4][TDEC_SEG];                // their destinati
 // MODE: 0 = DEC1 without a-priori (n = 0), 1 = DEC1 with a-priori, 2 = DEC2.  A compile-time mode keeps
 // every load unconditional (a runtime "load or zero" select makes hipcc branch around each load and
 // wait for it, which serialises the memory pipeline).
-// DIAG (diagnostic builds only, selected by MI355_TDEC_DIAG): 1 = backward pass only, 2 = forward only
+// DIAG (timing only, wrong results; selected by MI355_TDEC_DIAG / mi355_tdec_set_diag): 1 = backward pass only, 2 =
+// forward pass only, 3 = backward pass without its checkpoint stores, 4 = the backward pass's loads only, 20 = the
+// bandwidth-only clone (below)
 // FULL: L % SEG == 0 (every K whose window length is a multiple of 8, e.g. K = 6144): no ragged last segment,
 // so every segment-bound test folds at compile time and the unrolled steps stay one basic block.
 #ifndef TDEC_WAVES_PER_EU
 #define TDEC_WAVES_PER_EU 2
 #endif
-#ifndef TDEC_NPH
-#define TDEC_NPH 1
-#endif
-// forward pass: segments whose loads are in flight while one is consumed (2: the next one; 3: the next two, a third
-// register set)
-#ifndef TDEC_FPF
-#define TDEC_FPF 2
-#endif
-// the bandwidth-only clone (DIAG 20) with parts of its traffic removed (variant builds, tools/build_variant.sh): what
-// each part of the schedule costs -- NO_E: no extrinsic scatter, NO_CK: no checkpoint stores / loads, NO_FIN: the
-// forward pass loads no inputs, NO_TAB: no interleaver-table loads
-#ifndef TDEC_CLONE_NO_E
-#define TDEC_CLONE_NO_E 0
-#endif
-// NO_E with KEEP: the values the removed stores would have written are kept alive (an empty asm use), so the loads
-// that feed them stay in the clone.  Without it, a launch that emits no decisions has no other use of the forward
-// pass's values and the compiler drops the forward pass's input and checkpoint loads with the stores.
-#ifndef TDEC_CLONE_KEEP
-#define TDEC_CLONE_KEEP 0
-#endif
-// extrinsic / a-priori outputs of a whole segment staged in LDS and stored as 16-byte row pieces (0: A/B builds, each
-// output as a scattered 2-byte store)
-#ifndef TDEC_STAGE_OUT
-#define TDEC_STAGE_OUT 1
-#endif
-#ifndef TDEC_CLONE_NO_CK
-#define TDEC_CLONE_NO_CK 0
-#endif
-// STG: segment t's staged output rows are stored right after segment t+1's loads are issued, not at the end of
-// segment t.  vmcnt counts loads and stores together in issue order, so a store issued before a load is waited for
-// with that load: flushed at the end of segment t, the stores sat in front of the next prefetch and every segment's
-// load wait also waited for the previous segment's stores to be acknowledged
-#ifndef TDEC_DEFER_FLUSH
-#define TDEC_DEFER_FLUSH 0
-#endif
-// non-temporal (streaming) stores for the staged output rows (NT_OUT) and the beta checkpoints (NT_CK): neither is
-// re-read inside the launch by anyone but the storing wave (checkpoints) or at all (outputs, read by the next launch)
-#ifndef TDEC_NT_OUT
-#define TDEC_NT_OUT 0
-#endif
-#ifndef TDEC_NT_CK
-#define TDEC_NT_CK 0
-#endif
-// buffer stores with an explicit cache policy for the staged output rows (TDEC_OUT_AUX) and the checkpoints
-// (TDEC_CK_AUX): -1 = plain global stores; 16 = sc1 (write-through), 2 = nt, 17 = sc0 sc1
-#ifndef TDEC_OUT_AUX
-#define TDEC_OUT_AUX -1
-#endif
-#ifndef TDEC_CK_AUX
-#define TDEC_CK_AUX -1
-#endif
-#ifndef TDEC_CLONE_NO_FIN
-#define TDEC_CLONE_NO_FIN 0
-#endif
-#ifndef TDEC_CLONE_NO_TAB
-#define TDEC_CLONE_NO_TAB 0
-#endif
-#ifndef TDEC_CLONE_CK_HALF // every other checkpoint stored and loaded (the traffic of a 16-step spacing)
-#define TDEC_CLONE_CK_HALF 0
-#endif
+// Experiments this body once carried as build switches or further DIAG values, removed with their results kept (the
+// code is in the history before this commit): the two-phase beta rebuild with 4 rows live (profiles/r06/map_w3/ab.txt),
+// a third forward register set (profiles/r05/clone_ab.txt "fpf"), unstaged 2-byte output stores (clone_ab.txt "stg"),
+// the deferred flush of the staged rows, non-temporal and explicit-cache-policy buffer stores for outputs and
+// checkpoints (profiles/r06/map_store_ab.txt, map_write_counters.txt), the clone with parts of its traffic removed or
+// kept alive (profiles/r05/clone_ab.txt, profiles/r06/map_clone_keep.txt), and the cache-resident bounds -- forward
+// inputs, checkpoint loads and stores served from group 0, every other checkpoint (DESIGN.md §4.1 "What bounds it",
+// profiles/r02f_mapexp/).
 // OUTK: what the half-iteration emits besides the extrinsic (compile time, so the forward loop has no per-step
 // branches): 0 nothing, 1 decision bytes (a.dec: DEC1 from registers, DEC2 through an LDS bitmap), 2 the decision
 // LLRs D (the decide kernel packs them)
@@ -296,6 +170,7 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
   constexpr int NL = NSB / 2;
   constexpr int G  = 64 / NL;
   static_assert(!TX || (NSB == 16 && FULL && SEG == 8), "TX loads need 8-lane rows and whole 8-step segments");
+  static_assert((DIAG >= 0 && DIAG <= 4) || DIAG == 20, "DIAG values the body knows");
   // the wave's group index is wave-uniform: readfirstlane keeps it (and every per-group base pointer) in SGPRs,
   // so stores address as SGPR base + 32-bit lane offset instead of per-lane 64-bit arithmetic
   const int     grp = __builtin_amdgcn_readfirstlane(gl >> 6), q = gl & 63;
@@ -330,9 +205,6 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
   const int       ys   = GI ? 64 : NL;
   const uint32_t* AP   = a.A1 + wg0;
   uint32_t*       ck   = a.ckpt + (size_t)grp * nseg * 8 * 64 + q;
-  // (TDEC_CK_AUX) the group's checkpoint block as a buffer resource, wave-uniform base
-  [[maybe_unused]] const __amdgpu_buffer_rsrc_t ckr =
-      __builtin_amdgcn_make_buffer_rsrc(a.ckpt + (size_t)grp * nseg * 8 * 64, 0, nseg * 8 * 64 * 4, 0x00020000);
 
   // TX: this lane's 16-byte piece of the code block it loads for (not its own), and the wave's transposition buffers
   const uint4*    txin  = nullptr;
@@ -480,13 +352,7 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
   }
   // ckpt[nseg-1] = row L (not normalised)
 #pragma unroll
-  for (int s = 0; s < 8; s++) {
-    if constexpr (DIAG == 9 || TDEC_NT_CK) {
-      __builtin_nontemporal_store(W(st[s]), &ck[((size_t)(nseg - 1) * 8 + s) * 64]);
-    } else {
-      ck[((size_t)(nseg - 1) * 8 + s) * 64] = W(st[s]);
-    }
-  }
+  for (int s = 0; s < 8; s++) ck[((size_t)(nseg - 1) * 8 + s) * 64] = W(st[s]);
 
   // ------------------------------------------------ backward pass: main, one checkpoint per segment
   {
@@ -541,22 +407,9 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
           }
           // (stored before the normalise below: the forward pass's output sums of the segment's last step take this
           // row as it is, saturating, so a normalised row without its zero state 0 would not be bit-exact)
-          if (i == 0 && t > 0 && DIAG != 3 && !(CL && TDEC_CLONE_NO_CK) && !(CL && TDEC_CLONE_CK_HALF && (t & 1))) {
+          if (i == 0 && t > 0 && DIAG != 3) {
 #pragma unroll
-            for (int s = 0; s < 8; s++) {
-              if constexpr (DIAG == 9 || TDEC_NT_CK) {
-                __builtin_nontemporal_store(W(st[s]), &ck[((size_t)(t - 1) * 8 + s) * 64]);
-              } else if constexpr (DIAG == 10) { // every other checkpoint only
-                if (t & 1) ck[((size_t)(t - 1) * 8 + s) * 64] = W(st[s]);
-              } else if constexpr (DIAG == 11 || (DIAG >= 100 && (DIAG & 4))) { // into group 0's region (cache resident)
-                a.ckpt[q + ((size_t)(t - 1) * 8 + s) * 64] = W(st[s]);
-              } else if constexpr (TDEC_CK_AUX >= 0) {
-                __builtin_amdgcn_raw_buffer_store_b32(W(st[s]), ckr, (int)((((t - 1) * 8 + s) * 64 + q) * 4), 0,
-                                                      TDEC_CK_AUX);
-              } else {
-                ck[((size_t)(t - 1) * 8 + s) * 64] = W(st[s]);
-              }
-            }
+            for (int s = 0; s < 8; s++) ck[((size_t)(t - 1) * 8 + s) * 64] = W(st[s]);
           }
           if (!CL && (i & 1) == 0 && k != 0) normalize<true>(st);
         }
@@ -614,24 +467,14 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
     }
   }
 
-  // Diagnostic builds that keep every computation alive but serve some traffic from cache (bounds on what removing it
-  // would gain): 6 = the forward pass reads its inputs from code block / group 0, 8 = checkpoint rows read from group
-  // 0's region, 11 = checkpoint stores into group 0's region; DIAG >= 100 combines them (bit 0 = 6, 1 = 8, 2 = 11).
-  // 9 = non-temporal checkpoint stores, 10 = every other checkpoint stored.
-  constexpr bool  FI  = DIAG == 6 || (DIAG >= 100 && (DIAG & 1));
-  const uint32_t* Xf  = FI ? (dec2 ? a.E + q : (const uint32_t*)a.in + l) : X;
-  const uint32_t* Yf  = FI ? (const uint32_t*)a.in + (dec2 ? (K + 32) : (K + 32) / 2) + l : Y;
-  const uint32_t* APf = FI ? a.A1 + q : AP;
-  const uint32_t* ckf = (DIAG == 8 || (DIAG >= 100 && (DIAG & 2))) ? a.ckpt + q : ck;
   // The extrinsic (DEC1: E for DEC2) or a-priori (DEC2: A1 for the next DEC1) outputs.  Every step of a wave fills
   // exactly one 256-byte row j' of the destination (the QPP interleaver is contention-free for windows of L steps), but
-  // as 128 scattered 2-byte lane stores, which cost the schedule a third of its time (bandwidth-only clone without
-  // them: 1.26 -> 0.82 ms per 65,536-CB launch, profiles/r05/clone_ab.txt).  STG (whole segments): the 8 steps' outputs
-  // are staged in LDS as the 8 rows they fill, [step][128 windows], and each code block's own lanes store its 32-byte
-  // slices of those rows as 16-byte pieces, two store instructions per segment instead of sixteen.
-  constexpr bool STG = FULL && !GI && TDEC_STAGE_OUT && (dec2 ? wr_a1 : wr_e) && !(CL && TDEC_CLONE_NO_E);
+  // as 128 scattered 2-byte lane stores.  STG (whole segments): the 8 steps' outputs are staged in LDS as the 8 rows
+  // they fill, [step][128 windows], and each code block's own lanes store its 32-byte slices of those rows as 16-byte
+  // pieces at the end of the segment, two store instructions per segment instead of sixteen (neutral to 2 %,
+  // profiles/r05/clone_ab.txt "stg"; the outputs cost their bytes' share of the launch, profiles/r06/map_clone_keep.txt).
+  constexpr bool STG = FULL && !GI && (dec2 ? wr_a1 : wr_e);
   int16_t*       O16 = dec2 ? A16 : E16;
-  [[maybe_unused]] const __amdgpu_buffer_rsrc_t outr = __builtin_amdgcn_make_buffer_rsrc(O16, 0, Lp * 256, 0x00020000);
   int16_t*       stg = nullptr;
   uint32_t*      stg_row = nullptr;
   if constexpr (STG) {
@@ -660,15 +503,7 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
         const int      idx = k * NL + l, r = idx / PPR, pc = idx % PPR;
         const uint32_t jr  = stg_row[r]; // the destination row of step r (shared by every window of it)
         const uint4    v   = *(const uint4*)(stg + r * 128 + 2 * lane0 + pc * 8);
-        typedef uint32_t u4v __attribute__((ext_vector_type(4)));
-        if constexpr (TDEC_OUT_AUX >= 0) {
-          __builtin_amdgcn_raw_buffer_store_b128((u4v){v.x, v.y, v.z, v.w}, outr,
-                                                 (int)(((size_t)jr * 128 + 2 * lane0 + pc * 8) * 2), 0, TDEC_OUT_AUX);
-        } else if constexpr (TDEC_NT_OUT) {
-          __builtin_nontemporal_store((u4v){v.x, v.y, v.z, v.w}, (u4v*)(O16 + (size_t)jr * 128 + 2 * lane0 + pc * 8));
-        } else {
-          *(uint4*)(O16 + (size_t)jr * 128 + 2 * lane0 + pc * 8) = v;
-        }
+        *(uint4*)(O16 + (size_t)jr * 128 + 2 * lane0 + pc * 8) = v;
       }
       // (the next segment's LDS writes follow these reads in the wave's in-order LDS queue; the fence keeps the
       // compiler from moving them above)
@@ -677,32 +512,21 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
     }
   };
   uint32_t cx[SEG], cy[SEG], ca[SEG] = {}, cd[SEG], cc[8];
-  constexpr bool NFIN = CL && TDEC_CLONE_NO_FIN, NTAB = CL && TDEC_CLONE_NO_TAB, NCK = CL && TDEC_CLONE_NO_CK;
   auto     load = [&](int t, uint32_t* x, uint32_t* y, uint32_t* ap, uint32_t* d, uint32_t* c) {
-    if constexpr (TX && !NFIN) {
+    if constexpr (TX) {
       if constexpr (!dec2) tx_load(txoX, t * SEG, x);
       tx_load(txoY, t * SEG, y, true);
     }
 #pragma unroll
     for (int i = 0; i < SEG; i++) {
       const int j = FULL ? t * SEG + i : min(t * SEG + i, L - 1); // clamp the ragged last segment
-      if constexpr (NFIN) {
-        x[i] = y[i] = (uint32_t)j;
-      } else {
-        if constexpr (!TX || dec2) x[i] = Xf[j * xs];
-        if constexpr (!TX) y[i] = yrow(cbg, j) ? Yf[j * ys] : 0u;
-      }
-      if constexpr (has_ap) ap[i] = APf[j * 64];
-      if constexpr (NTAB) {
-        d[i] = (uint32_t)(j * 128 + 2 * l) | ((uint32_t)(j * 128 + 2 * l + 1) << 16);
-      } else {
-        d[i] = tab[(size_t)j * NL];
-      }
+      if constexpr (!TX || dec2) x[i] = X[j * xs];
+      if constexpr (!TX) y[i] = yrow(cbg, j) ? Y[j * ys] : 0u;
+      if constexpr (has_ap) ap[i] = AP[j * 64];
+      d[i] = tab[(size_t)j * NL];
     }
 #pragma unroll
-    for (int s = 0; s < 8; s++) {
-      c[s] = (NCK || (CL && TDEC_CLONE_CK_HALF && (t & 1))) ? (uint32_t)s : ckf[((size_t)t * 8 + s) * 64];
-    }
+    for (int s = 0; s < 8; s++) c[s] = ck[((size_t)t * 8 + s) * 64];
   };
   load(0, cx, cy, ca, cd, cc);
 
@@ -724,10 +548,7 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
     const int s0 = t * SEG;
     const int e  = FULL ? s0 + SEG : ((s0 + SEG < L) ? s0 + SEG : L);
     uint32_t  bits = 0; // decision bits of the segment: window 2l in bits 8..15, 2l+1 in 0..7 (MSB first)
-    if (t + TDEC_FPF - 1 < nseg) load(t + TDEC_FPF - 1, nx, ny, na, nd, nc);
-    if constexpr (TDEC_DEFER_FLUSH) {
-      if (t > 0) flush(); // the previous segment's rows, behind this segment's prefetch
-    }
+    if (t + 1 < nseg) load(t + 1, nx, ny, na, nd, nc);
 
     v2s xin[SEG];
 #pragma unroll
@@ -739,16 +560,10 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
       }
     }
 
-    // Beta rows s0+1 .. e are rebuilt from the checkpoint (row e) in two halves so that only 4 rows
-    // are live at a time (the upper half is recomputed twice): phase A keeps rows 1..4 for alpha
-    // steps 0..3, phase B rows 5..8 for alpha steps 4..7.
-    // (TDEC_NPH = 1: all 8 rows live, one pass -- 32 more VGPRs, 2 fewer beta steps per segment)
-    static_assert(SEG == 8, "two-phase recompute assumes 8-row segments");
-    constexpr int NPH = CL ? 0 : TDEC_NPH, RP = 8 / TDEC_NPH;
-    v2s ck8[8], cur[8], R[RP][8];
+    static_assert(SEG == 8, "the rebuild keeps the 8 rows of a segment in registers");
+    v2s ck8[8];
 #pragma unroll
     for (int s = 0; s < 8; s++) ck8[s] = U(cc[s]);
-    const bool ck_norm = (e & 1) == 0 && e != L;
     if constexpr (CL) { // the clone: one xor per step in place of the beta rebuild, alpha and output; same stores
 #pragma unroll
       for (int i = 0; i < SEG; i++) {
@@ -756,16 +571,15 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
         if (FULL ? i < SEG : j < e) {
           const v2s      out = xin[i] ^ U(cy[i]) ^ ck8[i] ^ st[i];
           const uint32_t tb  = cd[i];
-          if constexpr (TDEC_CLONE_NO_E && TDEC_CLONE_KEEP) asm volatile("" ::"v"(out), "v"(tb));
           if constexpr (!dec2) {
-            if constexpr (wr_e && !TDEC_CLONE_NO_E) put(i, tb, out);
+            if constexpr (wr_e) put(i, tb, out);
             bits |= ((uint32_t)(out.x > 0) << (15 - i)) | ((uint32_t)(out.y > 0) << (7 - i));
             if constexpr (wr_bm) {
               bm_set(bm, 2 * l * L + j, out.x > 0);
               bm_set(bm, (2 * l + 1) * L + j, out.y > 0);
             }
           } else {
-            if constexpr (wr_a1 && !TDEC_CLONE_NO_E) put(i, tb, out);
+            if constexpr (wr_a1) put(i, tb, out);
             if constexpr (wr_bm) {
               const uint32_t jd = (tb & 0xffffu) >> 7, wlo = tb & 15u, whi = (tb >> 16) & 15u;
               bm_set(bm, wlo * L + jd, out.x > 0);
@@ -774,110 +588,92 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
           }
         }
       }
-    }
-
-#pragma unroll
-    for (int ph = 0; ph < NPH; ph++) {
-      const int lo = 1 + ph * RP; // rows kept in this phase: lo .. lo+RP-1
+    } else {
+      // Beta rows s0+1 .. e are rebuilt from the checkpoint (row e) in one pass with all 8 rows live: R[i - 1] is row
+      // s0 + i, the row alpha step i - 1 takes.  The stored checkpoint is not normalised (backward pass); the recursion
+      // continues from it normalised where the backward pass normalised it after the store.
+      v2s        cur[8], R[8][8];
+      const bool ck_norm = (e & 1) == 0 && e != L;
 #pragma unroll
       for (int s = 0; s < 8; s++) cur[s] = ck8[s];
       if (ck_norm) normalize<true>(cur);
 #pragma unroll
-      for (int i = SEG; i >= lo; i--) {
+      for (int i = SEG; i >= 1; i--) {
         const int j = s0 + i;
         if (FULL ? i == SEG : j == e) {
-          if (i <= lo + RP - 1) {
 #pragma unroll
-            for (int s = 0; s < 8; s++) R[i - lo][s] = ck8[s];
-          }
+          for (int s = 0; s < 8; s++) R[i - 1][s] = ck8[s];
         } else if (FULL ? i < SEG : j < e) {
           v2s row[8];
           beta_step<true>(cur, xin[i], U(cy[i]), row);
 #pragma unroll
           for (int s = 0; s < 8; s++) cur[s] = row[s];
-          if (i <= lo + RP - 1) {
 #pragma unroll
-            for (int s = 0; s < 8; s++) R[i - lo][s] = row[s];
-          }
+          for (int s = 0; s < 8; s++) R[i - 1][s] = row[s];
           if ((j & 1) == 0) normalize<true>(cur);
         }
       }
-      // alpha steps lo-1 .. lo+2 with outputs
+      // alpha steps 0 .. 7 with outputs
 #pragma unroll
-      for (int ii = 0; ii < RP; ii++) {
-        const int i = lo - 1 + ii;
+      for (int i = 0; i < SEG; i++) {
         const int j = s0 + i;
-      if (FULL ? i < SEG : j < e) {
-        v2s c0[8], c1[8];
-        alpha_cands<true>(st, xin[i], U(cy[i]), c0, c1);
-        // max over the 8 states as a tree (max is exact, so the order is free): no serial dependency chain
-        v2s t0[8], t1[8];
+        if (FULL ? i < SEG : j < e) {
+          v2s c0[8], c1[8];
+          alpha_cands<true>(st, xin[i], U(cy[i]), c0, c1);
+          // max over the 8 states as a tree (max is exact, so the order is free): no serial dependency chain
+          v2s t0[8], t1[8];
 #pragma unroll
-        for (int s = 0; s < 8; s++) {
-          t0[s] = sadd(R[ii][s], c0[s]);
-          t1[s] = sadd(R[ii][s], c1[s]);
-        }
-        const v2s m0 = vmax(vmax(vmax(t0[0], t0[1]), vmax(t0[2], t0[3])), vmax(vmax(t0[4], t0[5]), vmax(t0[6], t0[7])));
-        const v2s m1 = vmax(vmax(vmax(t1[0], t1[1]), vmax(t1[2], t1[3])), vmax(vmax(t1[4], t1[5]), vmax(t1[6], t1[7])));
-        const v2s out = ssub(m1, m0);
+          for (int s = 0; s < 8; s++) {
+            t0[s] = sadd(R[i][s], c0[s]);
+            t1[s] = sadd(R[i][s], c1[s]);
+          }
+          const v2s m0 = vmax(vmax(vmax(t0[0], t0[1]), vmax(t0[2], t0[3])), vmax(vmax(t0[4], t0[5]), vmax(t0[6], t0[7])));
+          const v2s m1 = vmax(vmax(vmax(t1[0], t1[1]), vmax(t1[2], t1[3])), vmax(vmax(t1[4], t1[5]), vmax(t1[6], t1[7])));
+          const v2s out = ssub(m1, m0);
 #pragma unroll
-        for (int s = 0; s < 8; s++) st[s] = vmax(c0[s], c1[s]);
-        if ((i & 1) == 0 && j != 0) normalize<true>(st);
+          for (int s = 0; s < 8; s++) st[s] = vmax(c0[s], c1[s]);
+          if ((i & 1) == 0 && j != 0) normalize<true>(st);
 
-        // destinations: j'*128 + window of this lane's two outputs (j' shared by every window of the CB)
-        const uint32_t tb  = cd[i];
-        const uint32_t olo = (tb & 0xffffu) + lane0 * 2, ohi = (tb >> 16) + lane0 * 2;
-        if constexpr (!dec2) {
-          // e = ext1 - app1 (wrapping), turbodecoder_iter.h:118-120 of the next DEC2
-          if constexpr (wr_e) put(i, tb, has_ap ? out - U(ca[i]) : out);
-          if constexpr (wr_d) WG_AT(a.D, j) = W(out);
-          bits |= ((uint32_t)(out.x > 0) << (15 - i)) | ((uint32_t)(out.y > 0) << (7 - i));
-          if constexpr (wr_bm) { // windows not byte-aligned: natural bits 2l L + j, (2l + 1) L + j
-            bm_set(bm, 2 * l * L + j, out.x > 0);
-            bm_set(bm, (2 * l + 1) * L + j, out.y > 0);
-          }
-        } else {
-          // a1 = app1 - ext1 (wrapping) of the next DEC1, turbodecoder_iter.h:108-110
-          if constexpr (wr_a1) put(i, tb, out - xin[i]);
-          if constexpr (wr_bm) { // natural bit w*L + j' (turbodecoder_win.h:973-993)
-            const uint32_t jd = (tb & 0xffffu) >> 7, wlo = tb & 15u, whi = (tb >> 16) & 15u;
-            bm_set(bm, wlo * L + jd, out.x > 0);
-            bm_set(bm, whi * L + jd, out.y > 0);
-          }
-          if constexpr (wr_d) {
-            D16[olo] = out.x;
-            D16[ohi] = out.y;
+          // destinations: j'*128 + window of this lane's two outputs (j' shared by every window of the CB)
+          const uint32_t tb  = cd[i];
+          const uint32_t olo = (tb & 0xffffu) + lane0 * 2, ohi = (tb >> 16) + lane0 * 2;
+          if constexpr (!dec2) {
+            // e = ext1 - app1 (wrapping), turbodecoder_iter.h:118-120 of the next DEC2
+            if constexpr (wr_e) put(i, tb, has_ap ? out - U(ca[i]) : out);
+            if constexpr (wr_d) WG_AT(a.D, j) = W(out);
+            bits |= ((uint32_t)(out.x > 0) << (15 - i)) | ((uint32_t)(out.y > 0) << (7 - i));
+            if constexpr (wr_bm) { // windows not byte-aligned: natural bits 2l L + j, (2l + 1) L + j
+              bm_set(bm, 2 * l * L + j, out.x > 0);
+              bm_set(bm, (2 * l + 1) * L + j, out.y > 0);
+            }
+          } else {
+            // a1 = app1 - ext1 (wrapping) of the next DEC1, turbodecoder_iter.h:108-110
+            if constexpr (wr_a1) put(i, tb, out - xin[i]);
+            if constexpr (wr_bm) { // natural bit w*L + j' (turbodecoder_win.h:973-993)
+              const uint32_t jd = (tb & 0xffffu) >> 7, wlo = tb & 15u, whi = (tb >> 16) & 15u;
+              bm_set(bm, wlo * L + jd, out.x > 0);
+              bm_set(bm, whi * L + jd, out.y > 0);
+            }
+            if constexpr (wr_d) {
+              D16[olo] = out.x;
+              D16[ohi] = out.y;
+            }
           }
         }
       }
     }
-    }
-    if constexpr (!TDEC_DEFER_FLUSH) flush();
+    flush(); // the segment's staged output rows
     if constexpr (wr_bits) { // turbodecoder_win.h:973-993: bit = LLR > 0, natural order, MSB first
       uint8_t* bb = (uint8_t*)bm + (size_t)(2 * l) * (L / 8) + t;
       bb[0]       = (uint8_t)(bits >> 8);
       bb[L / 8]   = (uint8_t)bits;
     }
   };
-#if TDEC_FPF == 3
-  // three register sets rotating by position (loop unrolled three times): set A holds segment t, B t + 1, and the
-  // free one receives t + 2
-  uint32_t mx[SEG], my[SEG], ma[SEG] = {}, md[SEG], mc[8];
-  if (nseg > 1) load(1, nx, ny, na, nd, nc);
-#pragma unroll 1
-  for (int t = 0; t < nseg; t += 3) {
-    fseg(t, cx, cy, ca, cd, cc, mx, my, ma, md, mc);
-    if (t + 1 < nseg) fseg(t + 1, nx, ny, na, nd, nc, cx, cy, ca, cd, cc);
-    if (t + 2 < nseg) fseg(t + 2, mx, my, ma, md, mc, nx, ny, na, nd, nc);
-  }
-#else
 #pragma unroll 1
   for (int t = 0; t < nseg; t += 2) {
     fseg(t, cx, cy, ca, cd, cc, nx, ny, na, nd, nc);
     if (t + 1 < nseg) fseg(t + 1, nx, ny, na, nd, nc, cx, cy, ca, cd, cc);
   }
-#endif
-  if constexpr (TDEC_DEFER_FLUSH) flush(); // the last segment's rows
   if constexpr (wr_bm || wr_bits) { // the code block's K/8 decision bytes, 8-byte stores by its NL lanes
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();

@@ -22,58 +22,11 @@
 #include "crc_device.h"
 #include "lds_optin.h"
 #include "tdec_internal.h"
+#include "tdec_trellis.h"
 
 namespace mi355 {
 
 namespace {
-
-typedef short v2s __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ v2s U2(uint32_t u) { return __builtin_bit_cast(v2s, u); }
-__device__ __forceinline__ uint32_t W2(v2s v) { return __builtin_bit_cast(uint32_t, v); }
-__device__ __forceinline__ v2s sadd2(v2s a, v2s b) { return __builtin_elementwise_add_sat(a, b); }
-__device__ __forceinline__ v2s ssub2(v2s a, v2s b) { return __builtin_elementwise_sub_sat(a, b); }
-__device__ __forceinline__ v2s vmax2(v2s a, v2s b) { return __builtin_elementwise_max(a, b); }
-__device__ __forceinline__ v2s spl(short s) { return (v2s){s, s}; }
-
-template <bool SAT> __device__ __forceinline__ v2s add2(v2s a, v2s b)
-{
-  if constexpr (SAT) {
-    return sadd2(a, b);
-  } else {
-    return a + b;
-  }
-}
-
-// turbodecoder_win.h:640-676 (beta) / :771-800 (alpha), state numbering as tdec_kernels.hip
-template <bool SAT> __device__ __forceinline__ void bstep(v2s s[8], v2s x, v2s y)
-{
-  const v2s xy = add2<SAT>(x, y);
-  v2s       n[8];
-  n[0] = vmax2(add2<SAT>(s[4], xy), s[0]);
-  n[1] = vmax2(s[4], add2<SAT>(s[0], xy));
-  n[2] = vmax2(add2<SAT>(s[5], y), add2<SAT>(s[1], x));
-  n[3] = vmax2(add2<SAT>(s[5], x), add2<SAT>(s[1], y));
-  n[4] = vmax2(add2<SAT>(s[6], x), add2<SAT>(s[2], y));
-  n[5] = vmax2(add2<SAT>(s[6], y), add2<SAT>(s[2], x));
-  n[6] = vmax2(s[7], add2<SAT>(s[3], xy));
-  n[7] = vmax2(add2<SAT>(s[7], xy), s[3]);
-#pragma unroll
-  for (int i = 0; i < 8; i++) s[i] = n[i];
-}
-
-__device__ __forceinline__ void acands(const v2s o[8], v2s x, v2s y, v2s c0[8], v2s c1[8])
-{
-  const v2s xy = sadd2(x, y);
-  c0[0] = o[0];            c1[0] = sadd2(o[1], xy);
-  c0[1] = sadd2(o[3], y);  c1[1] = sadd2(o[2], x);
-  c0[2] = sadd2(o[4], y);  c1[2] = sadd2(o[5], x);
-  c0[3] = o[7];            c1[3] = sadd2(o[6], xy);
-  c0[4] = o[1];            c1[4] = sadd2(o[0], xy);
-  c0[5] = sadd2(o[2], y);  c1[5] = sadd2(o[3], x);
-  c0[6] = sadd2(o[5], y);  c1[6] = sadd2(o[4], x);
-  c0[7] = o[6];            c1[7] = sadd2(o[7], xy);
-}
 
 // one code block in LDS, window-interleaved int16 [step k][window w] (u32 pair (2l, 2l+1) at k * NL + l)
 template <int NSB> struct Blk {
@@ -99,42 +52,46 @@ template <int NSB> struct Blk {
   }
   __device__ __forceinline__ void odd_xy(const uint32_t (&o)[6], v2s& x, v2s& y) const
   {
-    x = U2(__builtin_amdgcn_alignbit(o[1], o[0], 16));
-    if (has_ap) x = sadd2(x, U2(__builtin_amdgcn_alignbit(o[5], o[4], 16)));
-    y = U2(__builtin_amdgcn_alignbit(o[3], o[2], 16));
+    x = U(__builtin_amdgcn_alignbit(o[1], o[0], 16));
+    if (has_ap) x = sadd(x, U(__builtin_amdgcn_alignbit(o[5], o[4], 16)));
+    y = U(__builtin_amdgcn_alignbit(o[3], o[2], 16));
   }
 };
 
-// output LLR of a step from its alpha entering state, inputs and beta row (turbodecoder_win.h:771-832); the next
-// alpha state in s when adv
-__device__ __forceinline__ v2s out_llr(v2s s[8], v2s x, v2s y, const v2s (&row)[8], bool adv)
+// output LLR of a step from its alpha entering state, inputs and beta row (turbodecoder_win.h:771-832)
+__device__ __forceinline__ v2s out_llr(const v2s s[8], v2s x, v2s y, const v2s (&row)[8])
 {
   v2s c0[8], c1[8], t0[8], t1[8];
-  acands(s, x, y, c0, c1);
+  alpha_cands<true>(s, x, y, c0, c1);
 #pragma unroll
   for (int q = 0; q < 8; q++) {
-    t0[q] = sadd2(row[q], c0[q]);
-    t1[q] = sadd2(row[q], c1[q]);
+    t0[q] = sadd(row[q], c0[q]);
+    t1[q] = sadd(row[q], c1[q]);
   }
-  const v2s m0 = vmax2(vmax2(vmax2(t0[0], t0[1]), vmax2(t0[2], t0[3])), vmax2(vmax2(t0[4], t0[5]), vmax2(t0[6], t0[7])));
-  const v2s m1 = vmax2(vmax2(vmax2(t1[0], t1[1]), vmax2(t1[2], t1[3])), vmax2(vmax2(t1[4], t1[5]), vmax2(t1[6], t1[7])));
-  if (adv) {
+  const v2s m0 = vmax(vmax(vmax(t0[0], t0[1]), vmax(t0[2], t0[3])), vmax(vmax(t0[4], t0[5]), vmax(t0[6], t0[7])));
+  const v2s m1 = vmax(vmax(vmax(t1[0], t1[1]), vmax(t1[2], t1[3])), vmax(vmax(t1[4], t1[5]), vmax(t1[6], t1[7])));
+  return ssub(m1, m0);
+}
+
+// beta_step with the new row replacing the old one
+template <bool SAT> __device__ __forceinline__ void beta_inplace(v2s s[8], v2s x, v2s y)
+{
+  v2s n[8];
+  beta_step<SAT>(s, x, y, n);
 #pragma unroll
-    for (int q = 0; q < 8; q++) s[q] = vmax2(c0[q], c1[q]);
-  }
-  return ssub2(m1, m0);
+  for (int i = 0; i < 8; i++) s[i] = n[i];
 }
 
 __device__ __forceinline__ void st8(uint32_t* p, const v2s s[8])
 {
-  ((uint4*)p)[0] = make_uint4(W2(s[0]), W2(s[1]), W2(s[2]), W2(s[3]));
-  ((uint4*)p)[1] = make_uint4(W2(s[4]), W2(s[5]), W2(s[6]), W2(s[7]));
+  ((uint4*)p)[0] = make_uint4(W(s[0]), W(s[1]), W(s[2]), W(s[3]));
+  ((uint4*)p)[1] = make_uint4(W(s[4]), W(s[5]), W(s[6]), W(s[7]));
 }
 __device__ __forceinline__ void ld8(const uint32_t* p, v2s s[8])
 {
   const uint4 u = ((const uint4*)p)[0], v = ((const uint4*)p)[1];
-  s[0] = U2(u.x); s[1] = U2(u.y); s[2] = U2(u.z); s[3] = U2(u.w);
-  s[4] = U2(v.x); s[5] = U2(v.y); s[6] = U2(v.z); s[7] = U2(v.w);
+  s[0] = U(u.x); s[1] = U(u.y); s[2] = U(u.z); s[3] = U(u.w);
+  s[4] = U(v.x); s[5] = U(v.y); s[6] = U(v.z); s[7] = U(v.w);
 }
 
 // natural decision bit m (MSB first within its byte, turbodecoder_win.h:973-993) into the LDS bitmap
@@ -152,7 +109,7 @@ __device__ __forceinline__ void dbit(uint32_t* bits, uint32_t m, bool v)
 // successor then sit in lanes q and q ^ D (beta D = 4 >> K, alpha D = 1 << K) and each lane's successor is the
 // state it holds at phase K + 1 (the shift-register structure of the constituent code: beta successors 2j, 2j+1 of
 // j, j+4; alpha successors m, m+4 of 2m, 2m+1).  State 0 is always in lane q = 0.  The branch metric each lane adds
-// to its own and its partner's metric is one of 0, x, y, sat(x + y) (bstep / acands): by held state s, beta
+// to its own and its partner's metric is one of 0, x, y, sat(x + y) (tdec_trellis.h): by held state s, beta
 // (s & 3, 3 - (s & 3)), alpha (s >> 1, 3 - (s >> 1)) as (x bit, y bit) codes; the results are the register form's bit
 // for bit (same saturating operations on the same operands; max is symmetric).
 __device__ __forceinline__ uint32_t rotl3(uint32_t q, int K) { return ((q << K) | (q >> ((3 - K) % 3))) & 7u; }
@@ -187,24 +144,24 @@ __device__ __forceinline__ uint32_t lane_logical(uint32_t g) { return g ^ ((g & 
 // the value of logical lane q ^ D within each group of 8
 template <int D> __device__ __forceinline__ v2s partner(v2s v)
 {
-  const int w = (int)W2(v);
+  const int w = (int)W(v);
   if constexpr (D == 1) {
-    return U2((uint32_t)__builtin_amdgcn_mov_dpp(w, 0xB1, 0xF, 0xF, false)); // quad_perm [1,0,3,2]
+    return U((uint32_t)__builtin_amdgcn_mov_dpp(w, 0xB1, 0xF, 0xF, false)); // quad_perm [1,0,3,2]
   } else if constexpr (D == 2) {
-    return U2((uint32_t)__builtin_amdgcn_mov_dpp(w, 0x4E, 0xF, 0xF, false)); // quad_perm [2,3,0,1]
+    return U((uint32_t)__builtin_amdgcn_mov_dpp(w, 0x4E, 0xF, 0xF, false)); // quad_perm [2,3,0,1]
   } else {
-    return U2((uint32_t)__builtin_amdgcn_mov_dpp(w, 0x141, 0xF, 0xF, false)); // row_half_mirror: g ^ 7
+    return U((uint32_t)__builtin_amdgcn_mov_dpp(w, 0x141, 0xF, 0xF, false)); // row_half_mirror: g ^ 7
   }
 }
 // the value of group lane G in every lane of its group of 8 (quad broadcast, then the other quad by a row shift)
 template <int G> __device__ __forceinline__ v2s bcast(v2s v)
 {
   constexpr int qp = (G & 3) * 0x55; // quad_perm [G&3, G&3, G&3, G&3]
-  const int     b  = __builtin_amdgcn_mov_dpp((int)W2(v), qp, 0xF, 0xF, false);
+  const int     b  = __builtin_amdgcn_mov_dpp((int)W(v), qp, 0xF, 0xF, false);
   if constexpr (G < 4) {
-    return U2((uint32_t)__builtin_amdgcn_update_dpp(b, b, 0x114, 0xF, 0xA, false)); // row_shr:4 into lanes 4-7
+    return U((uint32_t)__builtin_amdgcn_update_dpp(b, b, 0x114, 0xF, 0xA, false)); // row_shr:4 into lanes 4-7
   } else {
-    return U2((uint32_t)__builtin_amdgcn_update_dpp(b, b, 0x104, 0xF, 0x5, false)); // row_shl:4 into lanes 0-3
+    return U((uint32_t)__builtin_amdgcn_update_dpp(b, b, 0x104, 0xF, 0x5, false)); // row_shl:4 into lanes 0-3
   }
 }
 // one trellis step at phase PH (saturating, turbodecoder_win.h:640-676 beta, :771-800 alpha)
@@ -212,9 +169,9 @@ template <bool BETA, int PH> __device__ __forceinline__ v2s dstep(v2s st, v2s x,
 {
   constexpr int D  = BETA ? (4 >> PH) : (1 << PH);
   const v2s     pr = partner<D>(st);
-  const v2s     go = sadd2(U2(W2(x) & c.mxo[PH]), U2(W2(y) & c.myo[PH]));
-  const v2s     gp = sadd2(U2(W2(x) & c.mxp[PH]), U2(W2(y) & c.myp[PH]));
-  return vmax2(sadd2(st, go), sadd2(pr, gp));
+  const v2s     go = sadd(U(W(x) & c.mxo[PH]), U(W(y) & c.myo[PH]));
+  const v2s     gp = sadd(U(W(x) & c.mxp[PH]), U(W(y) & c.myp[PH]));
+  return vmax(sadd(st, go), sadd(pr, gp));
 }
 // the step followed by turbodecoder_win.h:480-498's normalisation (16-bit: subtract the new state 0, held by logical
 // lane 0 = group lane 0 at every phase).  (Evaluating the new state 0 from the old states beside the step instead --
@@ -223,21 +180,15 @@ template <bool BETA, int PH> __device__ __forceinline__ v2s dstep(v2s st, v2s x,
 template <bool BETA, int PH> __device__ __forceinline__ v2s dstep_n(v2s st, v2s x, v2s y, const Lane8& c)
 {
   const v2s n = dstep<BETA, PH>(st, x, y, c);
-  return ssub2(n, bcast<0>(n));
+  return ssub(n, bcast<0>(n));
 }
 
 // output waves (A.owaves): staging buffers per recursion (chunks in flight between a recursion wave and its output
-// wave) and whether a waiting wave sleeps between polls (each wave has a SIMD of its own: polling costs no issue slots)
-#ifndef LAT_RING
-#define LAT_RING 2
-#endif
-#ifndef LAT_SPIN_SLEEP
-#define LAT_SPIN_SLEEP 0
-#endif
+// wave).  A waiting wave polls without sleeping (each wave has a SIMD of its own: polling costs no issue slots).  The
+// sleeping poll and the timing builds without output computation, passes or handoff are measured in
+// profiles/r06/lat_owaves/; their code is in the history before this commit.
+constexpr int LAT_RING = 2;
 static_assert(LAT_RING >= 2, "the recursion waves' own passes double-buffer");
-#ifndef LAT_DIAG
-#define LAT_DIAG 0 // (timing diagnostics, wrong results: 1 no output computation, 2 no output passes, 4 no output-wave handoff)
-#endif
 
 template <int P> struct Par {
   static constexpr int value = P;
@@ -336,7 +287,6 @@ __global__ __launch_bounds__(256) void tdec_win_lat(TdecLatArgs A)
         sflg[4] = 1;
         return false;
       }
-      if (LAT_SPIN_SLEEP) __builtin_amdgcn_s_sleep(1);
     }
     asm volatile("" ::: "memory"); // (the LDS reads after it are issued, and so performed, after the flag's)
     return true;
@@ -350,7 +300,7 @@ __global__ __launch_bounds__(256) void tdec_win_lat(TdecLatArgs A)
     if (lane == 0) *f = v;
   };
   const Lane8 cl = lane8((uint32_t)q, !alpha);
-  v2s         st   = spl(0);      // this lane's state
+  v2s         st   = splat(0);      // this lane's state
   int         ka = 0, pha = 0;    // alpha: next step and its phase
   int         kb = 0, phb = 0;    // beta: next row and the phase of the step computing it
   uint32_t*  sg    = sgb + (alpha ? 0 : LAT_RING * 64 * 8);
@@ -381,10 +331,10 @@ __global__ __launch_bounds__(256) void tdec_win_lat(TdecLatArgs A)
     const uint32_t* tbg = dec2 ? A.dstA : A.dstE; // [L][NL] output destinations (row j' * 128 + window per half)
     int16_t*        dst = (int16_t*)(dec2 ? a1 : ev);
     auto xin = [&](uint32_t xw, uint32_t yw, uint32_t aw, v2s& x, v2s& y, v2s& ap) {
-      ap = U2(aw);
-      x  = U2(xw);
-      if (has_ap) x = sadd2(x, ap);
-      y = U2(yw);
+      ap = U(aw);
+      x  = U(xw);
+      if (has_ap) x = sadd(x, ap);
+      y = U(yw);
     };
     // output of step k for pair pp (windows 2pp, 2pp+1): DEC1 E = out - a1 at the interleaved position, DEC2
     // A1 = out - E at the natural one; its decision bit at the natural position (DEC1: own, DEC2: the destination's)
@@ -432,7 +382,7 @@ __global__ __launch_bounds__(256) void tdec_win_lat(TdecLatArgs A)
       constexpr int ph = decltype(PH)::value;
       v2s           x, y;
       inp(k, x, y);
-      S[base + k * rs + p * 8 + (int)cl.held[ph]] = W2(st);
+      S[base + k * rs + p * 8 + (int)cl.held[ph]] = W(st);
       st = nrm ? dstep_n<false, ph>(st, x, y, cl) : dstep<false, ph>(st, x, y, cl);
     };
     // beta row k from row k+1 at phase PH (the row stored before its normalisation, at the phase after the step)
@@ -441,7 +391,7 @@ __global__ __launch_bounds__(256) void tdec_win_lat(TdecLatArgs A)
       v2s           x, y;
       inp(k, x, y);
       const v2s n = dstep<true, ph>(st, x, y, cl);
-      S[base + k * rs + p * 8 + (int)cl.held[(ph + 1) % 3]] = W2(n); // (before the normalisation)
+      S[base + k * rs + p * 8 + (int)cl.held[(ph + 1) % 3]] = W(n); // (before the normalisation)
       st = nrm ? dstep_n<true, ph>(st, x, y, cl) : n;
     };
     // 8 steps from k with the phase P0 and the parity Q0 of k template constants (normalisations placed at compile
@@ -452,7 +402,7 @@ __global__ __launch_bounds__(256) void tdec_win_lat(TdecLatArgs A)
       load8(k, 1, xv, yv);
       sfor<0, 8>([&](auto I) {
         constexpr int i = decltype(I)::value, ph = (P + i) % 3;
-        S[base + (k + i) * rs + p * 8 + (int)cl.held[ph]] = W2(st);
+        S[base + (k + i) * rs + p * 8 + (int)cl.held[ph]] = W(st);
         if constexpr (((Q + i) & 1) == 0) {
           st = dstep_n<false, ph>(st, xv[i], yv[i], cl);
         } else {
@@ -467,7 +417,7 @@ __global__ __launch_bounds__(256) void tdec_win_lat(TdecLatArgs A)
       sfor<0, 8>([&](auto I) {
         constexpr int i = decltype(I)::value, ph = (P + i) % 3;
         const v2s n = dstep<true, ph>(st, xv[i], yv[i], cl);
-        S[base + (k - i) * rs + p * 8 + (int)cl.held[(ph + 1) % 3]] = W2(n); // (before the normalisation)
+        S[base + (k - i) * rs + p * 8 + (int)cl.held[(ph + 1) % 3]] = W(n); // (before the normalisation)
         if constexpr (((Q + i) & 1) == 0) {
           st = dstep_n<true, ph>(st, xv[i], yv[i], cl);
         } else {
@@ -519,7 +469,7 @@ __global__ __launch_bounds__(256) void tdec_win_lat(TdecLatArgs A)
     // ------------------------------------------------ first parts: alpha over [0, H), beta over rows L .. H+1
     constexpr int RS = NL * 8; // words per step of a state array
     if (rec) {
-      st = spl(-TDEC_INF);
+      st = splat(-TDEC_INF);
       if (alpha) {
         // alpha entering step 0 of windows (2p, 2p+1): 40 steps over the last steps of windows (2p-1, 2p) from -INF
         // (turbodecoder_win.h:705-757); window 0 starts in state 0 (lane q = 0 at every phase)
@@ -566,11 +516,11 @@ __global__ __launch_bounds__(256) void tdec_win_lat(TdecLatArgs A)
         if (p == NL - 1) {
           const int16_t* T = tail + (dec2 ? 6 : 0);
           v2s            tr[8];
-          tr[0] = spl(0);
+          tr[0] = splat(0);
 #pragma unroll
-          for (int i = 1; i < 8; i++) tr[i] = spl(-TDEC_INF);
+          for (int i = 1; i < 8; i++) tr[i] = splat(-TDEC_INF);
 #pragma unroll
-          for (int tt = 2; tt >= 0; tt--) bstep<false>(tr, spl(T[2 * tt]), spl(T[2 * tt + 1]));
+          for (int tt = 2; tt >= 0; tt--) beta_inplace<false>(tr, splat(T[2 * tt]), splat(T[2 * tt + 1]));
           const uint32_t hs = cl.held[TDEC_WARMUP % 3];
           short          v  = tr[0].y;
 #pragma unroll
@@ -578,7 +528,7 @@ __global__ __launch_bounds__(256) void tdec_win_lat(TdecLatArgs A)
           st.y = v;
         }
         // row L is the beta row of step L-1; then rows L-1 .. H+1 (row k at bm[k-1-H])
-        bm[(L - 1 - H) * RS + p * 8 + (int)cl.held[TDEC_WARMUP % 3]] = W2(st);
+        bm[(L - 1 - H) * RS + p * 8 + (int)cl.held[TDEC_WARMUP % 3]] = W(st);
         kb = L - 1, phb = TDEC_WARMUP % 3;
         b_run(kb, L - 1 - H, phb, bm, -(1 + H) * RS, RS);
       }
@@ -593,7 +543,6 @@ __global__ __launch_bounds__(256) void tdec_win_lat(TdecLatArgs A)
       v2s      a8[8], row[8];
     };
     auto pass_load = [&](bool ok, int k, const uint32_t* as, const uint32_t* bs, uint32_t e, PassIn& P) {
-      if (LAT_DIAG & 2) return;
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -606,12 +555,11 @@ __global__ __launch_bounds__(256) void tdec_win_lat(TdecLatArgs A)
     };
     // fwd: the alpha wave's passes (step k = base + i_p), else the beta wave's (k = base + 7 - i_p)
     auto pass_do = [&](bool ok, int k, PassIn& P, bool fwd) {
-      if (LAT_DIAG & 3) return;
       bool dx = false, dy = false;
       if (ok) {
         v2s x, y, ap;
         xin(P.xw, P.yw, P.aw, x, y, ap);
-        const v2s out = out_llr(P.a8, x, y, P.row, false);
+        const v2s out = out_llr(P.a8, x, y, P.row);
         put(k, lp, P.e, x, ap, out);
         dx = out.x > 0, dy = out.y > 0;
       }
@@ -630,9 +578,7 @@ __global__ __launch_bounds__(256) void tdec_win_lat(TdecLatArgs A)
         }
       }
     };
-    if (ow && (LAT_DIAG & 4)) {
-      // (diagnostic: no handoff at all -- the output waves idle, the recursion waves neither wait nor post)
-    } else if (ow) {
+    if (ow) {
       // Output waves (A.owaves): the recursion waves only stage each chunk's PB steps of states and post the chunk
       // (cnt); wave 2 / 3 computes the alpha / beta wave's passes from them and posts each chunk it has read (rd), so
       // the output math no longer sits in the recursion's serial path.  LAT_RING staging buffers per recursion: chunk c
@@ -669,16 +615,16 @@ __global__ __launch_bounds__(256) void tdec_win_lat(TdecLatArgs A)
     } else if (OW && alpha) { // (a progress read that did not block measured slower: r06o2c)
       for (int k0 = H, c = 0; k0 < L; k0 += PB, c++) {
         const int n = min(PB, L - k0);
-        if (!(LAT_DIAG & 4) && c >= LAT_RING && !flag_wait(&sflg[1], (uint32_t)(c - LAT_RING + 1))) break; // chunk c - LAT_RING read
+        if (c >= LAT_RING && !flag_wait(&sflg[1], (uint32_t)(c - LAT_RING + 1))) break; // chunk c - LAT_RING read
         if (rec) a_run(ka, n, pha, sg + (c % LAT_RING) * 64 * 8, -k0 * RS, RS);
-        if (!(LAT_DIAG & 4)) flag_post(&sflg[0], (uint32_t)c + 1);
+        flag_post(&sflg[0], (uint32_t)c + 1);
       }
     } else if (OW && wv == bw) {
       for (int k0 = H, c = 0; k0 >= 1; k0 -= PB, c++) {
         const int n = min(PB, k0);
-        if (!(LAT_DIAG & 4) && c >= LAT_RING && !flag_wait(&sflg[3], (uint32_t)(c - LAT_RING + 1))) break;
+        if (c >= LAT_RING && !flag_wait(&sflg[3], (uint32_t)(c - LAT_RING + 1))) break;
         if (rec) b_run(kb, n, phb, sg + (c % LAT_RING) * 64 * 8, k0 * RS, -RS);
-        if (!(LAT_DIAG & 4)) flag_post(&sflg[2], (uint32_t)c + 1);
+        flag_post(&sflg[2], (uint32_t)c + 1);
       }
     } else if (!OW && alpha) {
       PassIn P{};

@@ -24,7 +24,7 @@ NHALF = 8
 SEED = 3
 TDEC_SEG = 8          # tdec_internal.h:11
 TDEC_GEN_CB_L = 12    # tdec_internal.h:87
-LAT_RING = 2          # tdec_win_lat.hip:232
+LAT_RING = 2          # tdec_win_lat.hip:190
 SB_STRIDE = 18600     # dlsch_internal.h:6: int16 per softbuffer slot, the input stride of every DL-SCH decode
 
 # (Eb/N0 in oracle.make_cb's convention, scale) of the codeword classes; the others are built in block()

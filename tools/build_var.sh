@@ -1,7 +1,7 @@
 #!/bin/bash
 # A variant build of the product library for same-box A/B timing: one source compiled with extra flags, linked with
 # the other objects of the current build into srsran_amd/lib_var/<name>.so (load it with MI355_LIB=...).
-#   tools/build_var.sh <name> <csrc file> <flags...>     e.g. tools/build_var.sh latd1 tdec_win_lat.hip -DLAT_DIAG=1
+#   tools/build_var.sh <name> <csrc file> <flags...>     e.g. tools/build_var.sh w3 tdec_kernels.hip -DTDEC_WAVES_PER_EU=3
 set -e
 NAME=$1; SRC=$2; shift 2
 cd "$(dirname "$0")/../srsran_amd"

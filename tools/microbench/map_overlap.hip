@@ -3,7 +3,10 @@
 //   full    : tdec_win_halfit on all CBs
 //   bwd/fwd : the diagnostic builds (DIAG 1 = backward pass only, DIAG 2 = forward pass only) on all CBs
 //   concur  : backward on half of the CBs (stream 1) while forward runs on the other half (stream 2)
-// Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -I../../include -I../../srsran_amd/csrc map_overlap.hip [-DTDEC_NPH=1]
+// Build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -I../../include -I../../srsran_amd/csrc map_overlap.hip
+// (The cache-resident bounds -- forward inputs, checkpoint loads and stores served from group 0, non-temporal and
+// halved checkpoint stores -- were DIAG values of the body that are gone; results in profiles/r02f_mapexp/, code in the
+// history.)
 #include "../../srsran_amd/csrc/tdec_kernels.hip"
 
 #include <stdio.h>
@@ -153,20 +156,8 @@ int main(int argc, char** argv)
       float tx2 = time1([&] { hipLaunchKernelGGL((tdec_win_halfit<16, 8, 2, 0, true, 0, true>), dim3(blocks(ncb)), dim3(256), 0, s1, args(0, ncb)); }, 10);
       float to2 = time1([&] { hipLaunchKernelGGL((tdec_win_halfit<16, 8, 2, 0, true, 0, false>), dim3(blocks(ncb)), dim3(256), 0, s1, args(0, ncb)); }, 10);
       float to1 = time1([&] { full(s1, 0, ncb); }, 10);
-      float td6 = time1([&] { hipLaunchKernelGGL((tdec_win_halfit<16, 8, 1, 6, true, 0>), dim3(blocks(ncb)), dim3(256), 0, s1, args(0, ncb)); }, 10);
-      float te6 = time1([&] { hipLaunchKernelGGL((tdec_win_halfit<16, 8, 2, 6, true, 0>), dim3(blocks(ncb)), dim3(256), 0, s1, args(0, ncb)); }, 10);
-      printf("bounds: forward inputs cache-resident: DEC1 %.4f ms, DEC2 %.4f ms\n", td6, te6);
-      float t8 = time1([&] { hipLaunchKernelGGL((tdec_win_halfit<16, 8, 1, 8, true, 0>), dim3(blocks(ncb)), dim3(256), 0, s1, args(0, ncb)); }, 10);
-      float t9 = time1([&] { hipLaunchKernelGGL((tdec_win_halfit<16, 8, 1, 9, true, 0>), dim3(blocks(ncb)), dim3(256), 0, s1, args(0, ncb)); }, 10);
       float t3 = time1([&] { hipLaunchKernelGGL((tdec_win_halfit<16, 8, 1, 3, true, 0>), dim3(blocks(ncb)), dim3(256), 0, s1, args(0, ncb)); }, 10);
-      printf("DEC1: checkpoint loads from group 0 %.4f, non-temporal stores %.4f ms; backward without stores %.4f ms\n", t8, t9, t3);
-      float t10 = time1([&] { hipLaunchKernelGGL((tdec_win_halfit<16, 8, 1, 10, true, 0>), dim3(blocks(ncb)), dim3(256), 0, s1, args(0, ncb)); }, 10);
-      float t11 = time1([&] { hipLaunchKernelGGL((tdec_win_halfit<16, 8, 1, 11, true, 0>), dim3(blocks(ncb)), dim3(256), 0, s1, args(0, ncb)); }, 10);
-      printf("DEC1: half the checkpoint stores %.4f, checkpoint stores to group 0 %.4f ms\n", t10, t11);
-      float c3 = time1([&] { hipLaunchKernelGGL((tdec_win_halfit<16, 8, 1, 103, true, 0>), dim3(blocks(ncb)), dim3(256), 0, s1, args(0, ncb)); }, 10);
-      float c7 = time1([&] { hipLaunchKernelGGL((tdec_win_halfit<16, 8, 1, 107, true, 0>), dim3(blocks(ncb)), dim3(256), 0, s1, args(0, ncb)); }, 10);
-      float c6 = time1([&] { hipLaunchKernelGGL((tdec_win_halfit<16, 8, 1, 106, true, 0>), dim3(blocks(ncb)), dim3(256), 0, s1, args(0, ncb)); }, 10);
-      printf("DEC1 cached: fwd inputs + ckpt loads %.4f, + ckpt stores %.4f, ckpt loads + stores %.4f ms\n", c3, c7, c6);
+      printf("DEC1: backward without stores %.4f ms\n", t3);
       {
         uint8_t* dec;
         CK(hipMalloc(&dec, (size_t)ncb * (K / 8)));
