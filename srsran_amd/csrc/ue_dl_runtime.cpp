@@ -13,6 +13,7 @@
 #include <string.h>
 #include <vector>
 
+#include "../../include/srsran_amd/csi.h"
 #include "../../include/srsran_amd/pdcch.h"
 #include "../../include/srsran_amd/pdsch.h"
 #include "../../include/srsran_amd/phich.h"
@@ -21,6 +22,7 @@
 #include "device_mem.h"
 #include "lte_common.h"
 #include "runtime_internal.h"
+#include "csi_internal.h"
 #include "host_parallel.h"
 #include "host_staging.h"
 #include "pdcch_runtime.h"
@@ -69,6 +71,8 @@ struct mi355_ue_dl {
   hipStream_t    side     = nullptr;       // estimator read-back + fill_res overlapping the PDSCH decode
   hipEvent_t     ev_chest = nullptr;
   CtrlState*     ctrl     = nullptr;       // PCFICH / PDCCH stage, built on first use
+  DevScratch     d_csi;                    // CSI feedback: a call's descriptors | result records
+  HostStaging    st_csi, back_csi;
   std::vector<std::unique_ptr<mi355::PdschPending>> pend; // find_and_decode: per chunk, decodes left in flight
   uint32_t       chunks = 0;                              // find_and_decode chunk count (0: automatic)
   uint32_t       ce_rows = 0;                             // batched calls: 1 = AVERAGE estimate row 0 only (set_ce_rows)
@@ -1043,6 +1047,66 @@ int mi355_ue_dl_decode_phich_batch(mi355_ue_dl_t* q, const mi355_dl_sf_job_t* sf
                           stream ? (hipStream_t)stream : q->own, out.data())))
     return r;
   for (size_t k = 0; k < dev.size(); k++) res[which[k]] = mi355_phich_res_t{MI355_SUCCESS, out[k].ack, out[k].distance};
+  return MI355_SUCCESS;
+}
+
+// the per-TTI feedback of srslte_ue_dl_gen_cqi_periodic / _aperiodic (ue_dl.c:886-1010) per subframe: descriptors up,
+// one csi_feedback launch, 32 bytes per subframe back, the decisions on the host
+int mi355_ue_dl_csi_batch(mi355_ue_dl_t* q, const mi355_dl_sf_job_t* sfjobs, const mi355_chest_dl_res_t* chest,
+                          uint32_t nsf, float snr_to_cqi_offset, mi355_csi_res_t* res, void* stream)
+{
+  if (!q || (nsf && (!sfjobs || !chest || !res))) return MI355_ERROR_INVALID_INPUTS;
+  // the one shape for which the reference computes the SINR lists and the condition number (csi.h)
+  if (q->cell.nof_ports != 2 || q->nof_rx != 2) return MI355_ERROR_INVALID_INPUTS;
+  // the sample counts (csi_internal.h) are those of a 14-symbol grid: an extended-CP grid holds 12 symbols, and
+  // sampling it as 14 would read past its end
+  if (q->cell.cp != MI355_CP_NORM) return MI355_ERROR_INVALID_INPUTS;
+  if (!nsf) return MI355_SUCCESS;
+  std::lock_guard<std::mutex> lock(q->mu);
+  CHECK_HIP(hipSetDevice(q->device));
+  hipStream_t  s     = stream ? (hipStream_t)stream : q->own;
+  const size_t b_job = staged_size((size_t)nsf * sizeof(CsiJob)), b_out = staged_size((size_t)nsf * sizeof(CsiOut));
+  // Nothing of an earlier call on this object is in flight (every call ends with a wait), so an outgrown arena could
+  // be freed -- but hipFree (SyncFree) waits for the whole device and would stall the other workers' streams.  Retire
+  // keeps the outgrown buffers until destruction instead: 72 bytes per subframe, grown by a quarter each time
+  CHECK_HIP(q->d_csi.reserve(b_job + b_out, b_job + b_out + (b_job + b_out) / 4, DevScratch::Retire));
+  char* base = q->d_csi.base();
+  CHECK_HIP(q->st_csi.reserve(b_job));
+  auto* cj = (CsiJob*)q->st_csi.slot((size_t)nsf * sizeof(CsiJob));
+  for (uint32_t i = 0; i < nsf; i++) {
+    for (uint32_t p = 0; p < 2; p++)
+      for (uint32_t r = 0; r < 2; r++) {
+        if (!sfjobs[i].ce[p][r]) return MI355_ERROR_INVALID_INPUTS;
+        cj[i].ce[p][r] = (const float2*)sfjobs[i].ce[p][r];
+      }
+    // srslte_precoding_pmi_select (precoding.c:2796): bound the noise estimate
+    const float n = chest[i].noise_estimate;
+    cj[i].noise   = (!std::isnormal(n) || n < 1e-9f) ? 1e-9f : n;
+    cj[i].pad     = 0;
+  }
+  CHECK_HIP(q->st_csi.upload(base, s));
+  CsiArgs a{};
+  a.jobs   = (const CsiJob*)base;
+  a.out    = (CsiOut*)(base + b_job);
+  a.nsf    = nsf;
+  a.n_cn   = csi_cn_samples(q->cell.nof_prb);
+  a.groups = csi_pmi_groups(q->cell.nof_prb);
+  // estimates written by the batched decode calls under set_ce_rows(1) have row 0 only
+  a.ce_row = q->ce_rows == 1 ? 12 * q->cell.nof_prb : 0u;
+  CHECK_HIP(csi_launch(a, s));
+  CHECK_HIP(q->back_csi.reserve((size_t)nsf * sizeof(CsiOut)));
+  CHECK_HIP(stage_copy(q->back_csi.host, a.out, (size_t)nsf * sizeof(CsiOut), s));
+  CHECK_HIP(wait_stream(s));
+  const CsiOut* o = (const CsiOut*)q->back_csi.host;
+  for (uint32_t i = 0; i < nsf; i++) {
+    mi355_csi_res_t& r = res[i];
+    memset(&r, 0, sizeof(r));
+    memcpy(r.sinr_1l, o[i].sinr_1l, sizeof(r.sinr_1l));
+    memcpy(r.sinr_2l, o[i].sinr_2l, sizeof(r.sinr_2l));
+    r.cn       = o[i].cn;
+    r.cn_count = o[i].cn_count;
+    mi355_csi_decide(chest[i].noise_estimate, snr_to_cqi_offset, &r);
+  }
   return MI355_SUCCESS;
 }
 
