@@ -1,5 +1,5 @@
 // srsran_amd/csrc/csi_internal.h -- records shared by the CSI feedback kernel (csi_kernels.hip), its runtime
-// (mi355_ue_dl_csi_batch in ue_dl_runtime.cpp) and the host decisions (csi_host.cpp).
+// (mi355_ue_dl_csi_batch in ue_dl_feedback.cpp) and the host decisions (csi_host.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 

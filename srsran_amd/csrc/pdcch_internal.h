@@ -1,5 +1,5 @@
 // srsran_amd/csrc/pdcch_internal.h -- descriptors shared by the control-channel kernels (pdcch_kernels.hip) and
-// their host runtime (pdcch_host.cpp / ue_dl_runtime.cpp).
+// their host runtime (pdcch_host.cpp / pdcch_runtime.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

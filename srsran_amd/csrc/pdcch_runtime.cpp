@@ -6,14 +6,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
-#include <chrono>
 #include <stdlib.h>
 #include <stdio.h>
 #include <string.h>
 #include <vector>
 
 #include "device_mem.h"
+#include "host_env.h"
 #include "host_staging.h"
 #include "lte_common.h"
 #include "pdcch_internal.h"
@@ -123,17 +122,18 @@ int CtrlState::phich(const mi355_dl_sf_job_t* sfjobs, const mi355_dl_sf_cfg_t* s
 }
 
 int CtrlState::run(const mi355_dl_sf_job_t* sfjobs, const float* host_noise, const float* d_noise,
-                   const uint16_t* rntis, const mi355_ue_dl_cfg_t* cfgs, uint32_t n, hipStream_t s,
+                   const uint16_t* rntis, const mi355_ue_dl_cfg_t* cfgs, uint32_t n, uint32_t ce_row, hipStream_t s,
                    mi355_ctrl_res_t* res, mi355_dci_msg_t* msgs)
 {
   if (!n) return MI355_SUCCESS;
-  int r = launch(sfjobs, host_noise, d_noise, rntis, cfgs, n, 1, s);
+  int r = launch(sfjobs, host_noise, d_noise, rntis, cfgs, n, 1, ce_row, 0, s);
   return r ? r : finish(0, rntis, cfgs, res, msgs);
 }
 
 int CtrlState::launch(const mi355_dl_sf_job_t* sfjobs, const float* host_noise, const float* d_noise,
                       const uint16_t* rntis, const mi355_ue_dl_cfg_t* cfgs, uint32_t n, uint32_t nchunks,
-                      hipStream_t s, const std::function<int(uint32_t, uint32_t)>& front)
+                      uint32_t ce_row, uint32_t split0, hipStream_t s,
+                      const std::function<int(uint32_t, uint32_t)>& front)
 {
   if (!n) return MI355_SUCCESS;
   nchunks = std::max(1u, std::min(nchunks, n));
@@ -184,8 +184,7 @@ int CtrlState::launch(const mi355_dl_sf_job_t* sfjobs, const float* host_noise, 
   }
   // a one-subframe call (srsUE's per-TTI search): its two descriptors travel in the kernel arguments, no upload
   // (MI355_NO_INLINE_JOBS=1: uploaded, A/B timing)
-  static const bool inl_ok = !(getenv("MI355_NO_INLINE_JOBS") && atoi(getenv("MI355_NO_INLINE_JOBS")) != 0);
-  const bool        inl    = inl_ok && n == 1 && nchunks == 1;
+  const bool inl = env_inline_jobs() && n == 1 && nchunks == 1;
   if (!inl) CHECK_HIP(st->upload(base, s));
   float*    d_llr  = (float*)(base + b_jobs + b_blind);
   uint32_t* d_cfi  = (uint32_t*)(base + b_jobs + b_blind + b_llr);
@@ -265,8 +264,7 @@ int CtrlState::finish(uint32_t chunk, const uint16_t* rntis, const mi355_ue_dl_c
 {
   if (chunk >= chunk_end.size()) return MI355_ERROR_INVALID_INPUTS;
   CHECK_HIP(wait_event(ev[chunk]));
-  static const bool prof = getenv("MI355_HOST_PROF") != nullptr;
-  const auto        tr0  = std::chrono::steady_clock::now();
+  const HostTime    tr0  = host_now();
   const uint32_t    b    = chunk ? chunk_end[chunk - 1] : 0, e = chunk_end[chunk];
   const uint32_t* h_cfi  = (const uint32_t*)back->host;
   const float*    h_corr = (const float*)(back->host + b_cfi_);
@@ -315,9 +313,9 @@ int CtrlState::finish(uint32_t chunk, const uint16_t* rntis, const mi355_ue_dl_c
                                            ul_msgs.data() + (size_t)i * MI355_MAX_DCI_MSG, &ul_cnt[i]);
     }
   });
-  if (prof)
+  if (env_host_prof())
     fprintf(stderr, "[mi355 host] control stage: blind-search replay %.1f us for %u subframes\n",
-            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - tr0).count(), e - b);
+            host_us(tr0, host_now()), e - b);
   return MI355_SUCCESS;
 }
 

@@ -27,7 +27,6 @@ struct CtrlState {
   DciCand*     last_cand = nullptr;
   std::unordered_map<uint64_t, BlindJob> plans; // search plan per (rnti, subframe, UE configuration)
   std::vector<BlindJob>                  plan_of; // this call's plan per subframe
-  uint32_t                               ce_row = 0; // set by the caller: estimates time-invariant, read row 0
   // the format-0 messages the previous call's replay kept per subframe (ue_dl.c:521-529), drained by mi355_ue_dl_find_ul_dci_batch
   std::vector<mi355_dci_msg_t> ul_msgs; // [n][MI355_MAX_DCI_MSG]
   std::vector<uint32_t>        ul_cnt;  // [n], every launch() starts them at 0
@@ -48,16 +47,18 @@ struct CtrlState {
   int init(const mi355_cell_t& c, uint32_t nof_rx);
   // PCFICH + PDCCH LLRs + blind decoding of n subframes on s, then the blind-search replay (synchronous).
   // Noise per subframe from host_noise[i] or, when host_noise is null, from device memory d_noise[i].
+  // ce_row: 12 nof_prb where the kernels are to read row 0 of the estimates for every symbol, else 0
   int run(const mi355_dl_sf_job_t* sfjobs, const float* host_noise, const float* d_noise, const uint16_t* rntis,
-          const mi355_ue_dl_cfg_t* cfgs, uint32_t n, hipStream_t s, mi355_ctrl_res_t* res, mi355_dci_msg_t* msgs);
-  uint32_t split0 = 0; // launch(): first chunk's size with two chunks (0: n / 2)
+          const mi355_ue_dl_cfg_t* cfgs, uint32_t n, uint32_t ce_row, hipStream_t s, mi355_ctrl_res_t* res,
+          mi355_dci_msg_t* msgs);
   // run() in two halves: launch() enqueues the kernels and read-backs of n subframes in nchunks consecutive chunks
   // (one completion event each); finish(c) waits for chunk c only and replays its blind searches, so the host
   // works on chunk c while the GPU runs the later chunks (and whatever the caller enqueued after them)
+  // split0: the first chunk's size with two chunks (0: n / 2)
   // front(o, m), when given, enqueues what chunk [o, o + m) needs first (its OFDM and estimation) ahead of its kernels
   int launch(const mi355_dl_sf_job_t* sfjobs, const float* host_noise, const float* d_noise, const uint16_t* rntis,
-             const mi355_ue_dl_cfg_t* cfgs, uint32_t n, uint32_t nchunks, hipStream_t s,
-             const std::function<int(uint32_t, uint32_t)>& front = nullptr);
+             const mi355_ue_dl_cfg_t* cfgs, uint32_t n, uint32_t nchunks, uint32_t ce_row, uint32_t split0,
+             hipStream_t s, const std::function<int(uint32_t, uint32_t)>& front = nullptr);
   int finish(uint32_t chunk, const uint16_t* rntis, const mi355_ue_dl_cfg_t* cfgs, mi355_ctrl_res_t* res,
              mi355_dci_msg_t* msgs);
   // srslte_phich_decode for njobs (subframe, resource) pairs on s, synchronous: out[i] for every job.  The caller has

@@ -1,5 +1,5 @@
 // srsran_amd/csrc/wiener_bank.h -- the per-link Wiener estimator states of one device (wiener_runtime.cpp), shared by
-// the standalone mi355_wiener_dl_* API and the UE chain's estimator (ue_dl_runtime.cpp).
+// the standalone mi355_wiener_dl_* API and the UE chain's estimator (ue_dl_front.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 

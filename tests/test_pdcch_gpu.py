@@ -206,7 +206,7 @@ def _make_dci(D, cell, fmt, mcs, rnti):
     return d
 
 
-def _ctrl_subframes(case):
+def _ctrl_subframes(case, sf_idxs=(0, 2, 3, 6, 9)):
     """The control-channel cases' subframes: (cell, rnti, subs, expect), see test_find_and_decode_end_to_end"""
     from srsran_amd import pdcch as D
     from srsran_amd import pdsch as S
@@ -216,7 +216,7 @@ def _ctrl_subframes(case):
     cell = S.make_cell(nprb, ports, cid)
     rnti = 0x3C1A
     subs, expect = [], []
-    for sf_idx in (0, 2, 3, 6, 9):
+    for sf_idx in sf_idxs:
         cfi = 1 if mcs == 27 else 1 + sf_idx % 3  # MCS 27 (256QAM, TBS 97896) only fits a CFI-1 control region
         d = _make_dci(D, cell, fmt, mcs, rnti)
         m = D.pack(cell, d, sf_idx)

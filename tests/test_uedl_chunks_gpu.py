@@ -1,4 +1,4 @@
-"""find_and_decode's pipelined chunks (mi355_ue_dl_find_and_decode_batch, ue_dl_runtime.cpp): a batch split into 1,
+"""find_and_decode's pipelined chunks (mi355_ue_dl_find_and_decode_batch, ue_dl_find_decode.cpp): a batch split into 1,
 2 or 3 chunks -- chunk c's PDSCH/DL-SCH left in flight while the host replays chunk c+1's blind search -- must give
 exactly the results of one chunk: every TB's CRC flag, return code, average iteration count and payload bytes.
 
