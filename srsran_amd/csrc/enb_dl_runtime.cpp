@@ -19,6 +19,7 @@
 #include "../../include/srsran_amd/enb_dl.h"
 #include "../../include/srsran_amd/tdec.h"
 #include "device_mem.h"
+#include "dlsch_tables.h" // make_crc_table
 #include "enb_dl_internal.h"
 #include "host_staging.h"
 #include "lte_common.h"

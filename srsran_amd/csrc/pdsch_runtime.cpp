@@ -9,7 +9,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <stdlib.h>
 #include <cmath>
 #include <map>
@@ -25,6 +24,7 @@
 #include "../../include/srsran_amd/pdsch.h"
 #include "../../include/srsran_amd/tdec.h"
 #include "device_mem.h"
+#include "host_env.h"
 #include "host_staging.h"
 #include "lte_common.h"
 #include "pdsch_internal.h"
@@ -400,7 +400,7 @@ static void set_invariant(const mi355_pdsch_t* q, JobPlan& P, bool ce_invariant)
 static int run_frontend(mi355_pdsch_t* q, const mi355_pdsch_job_t* jobs, std::vector<JobPlan>& plans, hipStream_t s,
                         bool after_s = false, const EqRmPlan* er = nullptr)
 {
-  const auto     t_in  = std::chrono::steady_clock::now();
+  const HostTime t_in  = host_now();
   const uint32_t njobs = (uint32_t)plans.size();
   size_t         nd = 0, ne = 0;
   std::vector<PdschCwDev> cws;
@@ -540,9 +540,8 @@ static int run_frontend(mi355_pdsch_t* q, const mi355_pdsch_job_t* jobs, std::ve
       ci++;
     }
   }
-  static const bool prof = getenv("MI355_HOST_PROF") != nullptr;
-  auto              now  = [] { return std::chrono::steady_clock::now(); };
-  const auto        ta   = now();
+  const bool     prof = env_host_prof();
+  const HostTime ta   = host_now();
   q->stage.put(hj.data(), njobs * sizeof(PdschJobDev));
   q->stage.put(cws.data(), ncw * sizeof(PdschCwDev));
   q->stage.put(new_ci.data(), new_ci.size() * 4);
@@ -550,14 +549,14 @@ static int run_frontend(mi355_pdsch_t* q, const mi355_pdsch_job_t* jobs, std::ve
   if (er) q->stage.put(er->rj.data(), njobs * sizeof(EqRmJob));
   // after_s: the previous batch may still be in flight; its front end (the only reader of the descriptors) is done
   // at fe_done
-  const auto tb = now();
+  const HostTime tb = host_now();
   CHECK_HIP(q->stage.upload(base, s, after_s, after_s && q->fe_armed ? q->fe_done : nullptr));
-  const auto tc = now();
+  const HostTime tc = host_now();
   CHECK_HIP(pdsch_launch_equalize((const PdschJobDev*)(base + o_jobs), njobs, max_units, s));
-  const auto tl0 = now();
+  const HostTime tl0 = host_now();
   CHECK_HIP(pdsch_launch_scr_pack((const uint32_t*)(base + o_nci), (uint32_t* const*)(base + o_ndst),
                                   (uint32_t)new_ci.size(), q->gold.as<uint32_t>(), PDSCH_GOLD_MAX / 32, s));
-  const auto tl1 = now();
+  const HostTime tl1 = host_now();
   q->e_pending = er != nullptr;
   if (er) {
     CHECK_HIP(pdsch_launch_eq_rm((const PdschJobDev*)(base + o_jobs), (const EqRmJob*)(base + o_rj), njobs, er->max_c,
@@ -568,18 +567,17 @@ static int run_frontend(mi355_pdsch_t* q, const mi355_pdsch_job_t* jobs, std::ve
   else
     CHECK_HIP(pdsch_launch_fused((const PdschJobDev*)(base + o_jobs), njobs, max_fpairs, fkeys.data(),
                                  (uint32_t)fkeys.size(), s));
-  const auto tl2 = now();
+  const HostTime tl2 = host_now();
   CHECK_HIP(pdsch_launch_llr((const PdschCwDev*)(base + o_cws), (uint32_t)ncw, max_pairs, s));
-  const auto tl3 = now();
+  const HostTime tl3 = host_now();
   if (!q->fe_done) CHECK_HIP(hipEventCreateWithFlags(&q->fe_done, hipEventDisableTiming));
   CHECK_HIP(hipEventRecord(q->fe_done, s));
   q->fe_armed = true;
   if (prof) {
-    auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
     fprintf(stderr, "[mi355 host] pdsch frontend: tables %.1f us, put %.1f us, upload %.1f us, launches %.1f us "
                     "(equalize %.1f, scr %.1f, fused %.1f, llr %.1f, event %.1f)\n",
-            us(t_in, ta), us(ta, tb), us(tb, tc), us(tc, now()), us(tc, tl0), us(tl0, tl1), us(tl1, tl2), us(tl2, tl3),
-            us(tl3, now()));
+            host_us(t_in, ta), host_us(ta, tb), host_us(tb, tc), host_us(tc, host_now()), host_us(tc, tl0),
+            host_us(tl0, tl1), host_us(tl1, tl2), host_us(tl2, tl3), host_us(tl3, host_now()));
   }
   return MI355_SUCCESS;
 }
@@ -859,9 +857,8 @@ int mi355::pdsch_decode_batch_dev_noise(mi355_pdsch_t* q, mi355_softbuffer_pool_
 {
   if (!q || !pool || !res || (njobs && !jobs)) return MI355_ERROR_INVALID_INPUTS;
   std::lock_guard<std::mutex> lock(q->mu);
-  static const bool prof = getenv("MI355_HOST_PROF") != nullptr;
-  auto              now  = [] { return std::chrono::steady_clock::now(); };
-  const auto        t0   = now();
+  const bool     prof = env_host_prof();
+  const HostTime t0   = host_now();
   CHECK_HIP(hipSetDevice(q->device));
   hipStream_t          s = stream ? (hipStream_t)stream : q->own;
   std::vector<JobPlan> plans(njobs);
@@ -876,12 +873,12 @@ int mi355::pdsch_decode_batch_dev_noise(mi355_pdsch_t* q, mi355_softbuffer_pool_
   }
   EqRmPlan   er;
   const bool eqrm = plan_eq_rm(q, pool, jobs, plans, er);
-  const auto t1   = now();
+  const HostTime t1 = host_now();
   r               = run_frontend(q, jobs, plans, s, after_s, eqrm ? &er : nullptr);
   if (r) return r;
   if (prof) {
-    auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
-    fprintf(stderr, "[mi355 host] pdsch: plan %.1f us, frontend launch %.1f us\n", us(t0, t1), us(t1, now()));
+    fprintf(stderr, "[mi355 host] pdsch: plan %.1f us, frontend launch %.1f us\n", host_us(t0, t1),
+            host_us(t1, host_now()));
   }
   q->last.swap(plans);
   const std::vector<JobPlan>& plan = q->last;

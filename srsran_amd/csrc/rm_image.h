@@ -15,12 +15,7 @@ __host__ __device__ constexpr uint32_t img_i16(uint32_t r) { return r; }        
 __host__ __device__ constexpr uint32_t img_u32(uint32_t p) { return p; }                // u32 index of LLR pair p
 __host__ __device__ constexpr uint32_t img_elems(uint32_t n) { return (n + 7) / 8 * 8; } // int16 for n LLRs
 
-// Every 16-bit inverse rate-dematching table (decoder position -> circular index, buflen + 1 entries) is followed, at
-// u16 offset rm_rowmin_off(buflen), by 2 x 32 SB_ROWMASK_WORDS row minima: [stream P0, P1][row j] = the smallest
-// circular index among the row's 16 window positions (RM_NONE when none); rows j >= L = K / 16, and every row of a K
-// without the 16-window layout, hold 0 (always defined).
-__host__ __device__ constexpr uint32_t rm_rowmin_off(uint32_t buflen) { return (buflen + 1 + 7) / 8 * 8; }
-__host__ __device__ constexpr uint32_t rm_rowmin_len() { return 2 * 32 * SB_ROWMASK_WORDS; }
+// (the row minima behind every 16-bit inverse rate-dematching table: rm_rowmin_off / rm_rowmin_len, dlsch_layout.h)
 
 // Word w (< 2 SB_ROWMASK_WORDS) of a slot's parity-row bitmap (SB_ROWMASK, dlsch_internal.h) after a rate dematching
 // into it: a fresh buffer holds LLRs exactly in the rows whose minimum circular index is below min(E, N) (thr), a

@@ -11,6 +11,7 @@
 
 #include "../../include/srsran_amd/tdec.h"
 #include "device_mem.h"
+#include "dlsch_tables.h"
 #include "lte_qpp_table.h"
 #include "rm_tables.h"
 #include "tdec8_internal.h"
@@ -169,10 +170,7 @@ int mi355_rm_turbo_rx_8bit_dev(mi355_tdec8_t* q, const int8_t* e, size_t e_strid
   const uint64_t key = ((uint64_t)K << 2) | rv;
   DevMem*        m   = nullptr;
   int            r   = q->rm_inv.get(key, &m, [&](DevMem& d) -> int {
-    const std::vector<uint16_t> t = rm_rx_table_nsb(K, rv, nsb); // circular index -> decoder position
-    std::vector<uint16_t>       inv(buflen, 0xffff);
-    for (uint32_t i = 0; i < N; i++) inv[t[i]] = (uint16_t)i;
-    CHECK_HIP(d.upload(inv));
+    CHECK_HIP(d.upload(rm_inverse(K, rv, nsb, buflen, RM_NONE)));
     return MI355_SUCCESS;
   });
   if (r) return r;

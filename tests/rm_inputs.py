@@ -59,8 +59,8 @@ def table(K: int, rv: int) -> np.ndarray:
 
 @functools.lru_cache(maxsize=None)
 def rowmin(K: int, rv: int):
-    """16-window sizes: (2, L) smallest circular index among the 16 positions of each parity row (rm_image.h:18-21,
-    dlsch_runtime.cpp rm_table); None for the other sizes"""
+    """16-window sizes: (2, L) smallest circular index among the 16 positions of each parity row (dlsch_layout.h
+    rm_rowmin_off, dlsch_tables.h rm16_table); None for the other sizes"""
     if TI.nsb(K) != 16:
         return None
     inv = np.full(buflen(K, 16), 0xffff, np.int64)
@@ -133,13 +133,13 @@ def features(K: int, rv: int, E: int, e_offset: int, Qm: int = 2, fresh: bool = 
             "load": "e16" if e_offset % 8 == 0 and min(E, N) % 2 == 0 else "e4" if e_offset % 2 == 0 else "unaligned",
             "fresh": fresh,                                   # dlsch_kernels.hip:107: written whole instead of read
             "wraps": -(-E // N) - 1,                          # dlsch_kernels.hip:131: accumulating passes, E > N
-            "fold2": (min(E + Qm, N) + 1) // 2,               # dlsch_runtime.cpp:753-756: LDS pairs of the TB
+            "fold2": (min(E + Qm, N) + 1) // 2,               # dlsch_plan.h plan_tbs: LDS pairs of the TB
             "tail_quads": (buflen(K, n) // 2) % 4,            # dlsch_kernels.hip:156: pairs of the last, partial store
             "passes": -(-(buflen(K, n) // 2) // (4 * RM_THREADS)),  # dlsch_kernels.hip:141: quads per thread in use
-            "empty_rows": (P0, P1),                           # rm_image.h:25-28 (fresh 16-window buffers)
+            "empty_rows": (P0, P1),                           # rm_image.h rm_rowmask_word (fresh 16-window buffers)
             "sparse": n == 16 and 0 < P0 + P1,                # dlsch_kernels.hip:142: rows left unwritten
             "rows_mixed": n == 16 and 0 < P0 + P1 < 2 * (K // 16),
-            # pdsch_runtime.cpp:803-805: pdsch_eq_rm (and its compact tables, dlsch_runtime.cpp:627) only without wrap
+            # pdsch_runtime.cpp plan_eq_rm: pdsch_eq_rm (and its compact tables, dlsch_tables.h) only without wrap
             "eqrm_ok": E + Qm <= N}
 
 

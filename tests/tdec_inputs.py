@@ -131,7 +131,7 @@ def features(K: int) -> dict:
                "lat_bytes1": n == 16 and L % 16 == 0,          # tdec_win_lat.hip:393
                "lat_tail_fwd": (n, (L - H) % PB),              # tdec_win_lat.hip:646: min(PB, L - k0) of the last chunk
                "lat_tail_bwd": (n, H % PB),                    # tdec_win_lat.hip:658: min(PB, k0)
-               "lat_fits": lat_lds(K, n) <= 160 * 1024 - 64}   # tdec_win_lat.hip:765, dlsch_runtime.cpp:918
+               "lat_fits": lat_lds(K, n) <= 160 * 1024 - 64}   # tdec_win_lat.hip:765, dlsch_runtime.cpp launch_latency
     f.update(win)
     return f
 

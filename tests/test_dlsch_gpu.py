@@ -116,7 +116,7 @@ def test_dlsch_speculative_dec2_matches_oracle(max_its):
 
 
 def test_dlsch_many_distinct_tb_sizes_one_call():
-    """the TB epilogue's per-size CRC factor tables (dlsch_runtime.cpp tb_crc_scales) must stay valid for
+    """the TB epilogue's per-size CRC factor tables (dlsch_tables.h tb_crc_scales_table) must stay valid for
     every TB planned in a call.  530 distinct TB sizes (more than the old 512-entry cap) in one batch, then the first
     100 again in a second call; every TB passes its CRC with the transmitted payload.  Sizes: no filler bits and one
     code-block size per TB (the reference's TX orders mixed K+/K- blocks K- first and its RX K+ first, sch.c:255-265 vs
@@ -179,6 +179,60 @@ def test_null_stream_reset_done_before_decode(kind):
         want = _oracle([noise], [(tbs, Qm, G, 0.0)], [0], 4, [oracle.Softbuffer()])
         _check(got, want, [(tbs, Qm, G, 0.0)])
         assert got[0] == [-1], (rnd, got[0])
+
+
+def _decode_counted(dl, pool, desc, llrs, **kw):
+    """One decode with tdec_win_lat's phase counters armed: (results, the 11 counters)."""
+    import ctypes as C
+    counters = (C.c_uint64 * 11)()
+    check(lib().mi355_dlsch_latency_profile(1, None), "latency_profile")
+    try:
+        got = dl.decode(pool, desc, llrs, **kw)
+    finally:
+        check(lib().mi355_dlsch_latency_profile(0, C.addressof(counters)), "latency_profile")
+    return got, list(counters)
+
+
+def test_dlsch_latency_path_boundary():
+    """The latency path's limit counts the call's code blocks, inclusively, and never applies to int8 LLRs.  One call of
+    three single-block TBs -- K = 1024 (16 windows), K = 480 (8 windows), K = 64 (generic): 3 code blocks -- under a
+    limit of 3 (the two window blocks decode on tdec_win_lat: its counters run, [10] counts them) and of 2 (none does:
+    every counter stays zero); both results are the oracle's.  The same call with int8 LLRs (K = 280 in place of 480,
+    which the 8-bit mode rejects) leaves the counters zero under a limit of 512."""
+    cases = [(1000, 2, 3010, 1.0), (456, 2, 1500, 0.5), (40, 2, 200, -1.0)]
+    assert [oracle.cbsegm(t)["K1"] for t, *_r in cases] == [1024, 480, 64]
+    assert sum(oracle.cbsegm(t)["C"] for t, *_r in cases) == 3
+    rng = np.random.default_rng(3)
+    llrs = [oracle.make_tb(rng, t, q, g, 0, snr)[1] for (t, q, g, snr) in cases]
+    desc = [dict(tbs=t, Qm=q, rv=0, softbuffer=i) for i, (t, q, g, s) in enumerate(cases)]
+    want = _oracle(llrs, cases, [0] * 3, 6, [oracle.Softbuffer() for _ in cases])
+    old = lib().mi355_dlsch_set_latency_path(-1)
+    try:
+        dl = Dlsch(0, 6)
+        for limit in (3, 2):
+            lib().mi355_dlsch_set_latency_path(limit)
+            got, counters = _decode_counted(dl, SoftbufferPool(3, 2), desc, llrs)
+            _check(got, want, cases)
+            if limit == 3:
+                assert counters[10] == 2 and any(counters[:5]), counters  # [0, 5): phase cycles
+            else:
+                assert counters == [0] * 11, counters
+        lib().mi355_dlsch_set_latency_path(512)
+        cases8 = [(1000, 2, 3010), (256, 2, 1080), (40, 2, 200)]
+        bits = [rng.integers(0, 2, t, dtype=np.uint8) for t, _q, _g in cases8]
+        llrs8 = []
+        for b, (t, q, g) in zip(bits, cases8):
+            y = np.where(oracle.dlsch_encode_tb(b, t, q, g, 0).astype(bool), 1.0, -1.0) + 0.25 * rng.standard_normal(g)
+            llrs8.append(np.clip(np.round(20.0 * y), -127, 127).astype(np.int8))
+        desc8 = [dict(tbs=t, Qm=q, rv=0, softbuffer=i) for i, (t, q, g) in enumerate(cases8)]
+        (rets, datas, _its), counters = _decode_counted(dl, SoftbufferPool(3, 2), desc8, llrs8, llr8=True)
+        assert counters == [0] * 11, counters
+        assert rets == [0, 0, 0], rets
+        for i, (t, _q, _g) in enumerate(cases8):
+            np.testing.assert_array_equal(datas[i][: t // 8], np.packbits(bits[i]), err_msg=f"tbs={t}")
+        dl.close()
+    finally:
+        lib().mi355_dlsch_set_latency_path(old)
 
 
 # ------------------------------------------------------------------ every code-block size on both turbo paths

@@ -510,7 +510,7 @@ def test_rm_turbo_rx_8bit_every_size(rv):
     assert not bad, (len(bad), bad[:10])
 
 
-SIZES_DLSCH8 = tuple(K for K in TI.CB_SIZES if K <= 400 or TI.nsb8(K) >= 16)  # dlsch_runtime.cpp: ok8
+SIZES_DLSCH8 = tuple(K for K in TI.CB_SIZES if K <= 400 or TI.nsb8(K) >= 16)  # dlsch_plan.h: dlsch_k_ok8
 
 
 @gpu
