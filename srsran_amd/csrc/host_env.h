@@ -1,5 +1,5 @@
-// srsran_amd/csrc/host_env.h -- the environment knobs of the host runtimes (ue_dl, control stage, DL-SCH), each read once
-// (INTEGRATION.md lists them), and the clock behind the "[mi355 host]" phase timings.
+// srsran_amd/csrc/host_env.h -- the environment knobs of the host runtimes (ue_dl, control stage, PDSCH, DL-SCH), each read
+// once unless it says otherwise (INTEGRATION.md lists them), and the clock behind the "[mi355 host]" phase timings.
 #pragma once
 #include <chrono>
 #include <stdint.h>
@@ -32,6 +32,14 @@ inline bool env_lat_waves4() { static const bool v = env_int("MI355_LAT_WAVES") 
 inline bool env_lat_owaves() { static const bool v = !getenv("MI355_LAT_OWAVES") || env_int("MI355_LAT_OWAVES") != 0; return v; }
 // MI355_RM_SPARSE=0 (A/B timing): fresh decoder buffers written whole, zero parity rows included
 inline bool env_rm_sparse() { static const bool v = !getenv("MI355_RM_SPARSE") || env_int("MI355_RM_SPARSE") != 0; return v; }
+
+// MI355_NO_EQRM (A/B, tests): never pdsch_eq_rm.  Set means present, whatever the value; read on every call (tests set
+// and clear it within one process)
+inline bool env_no_eqrm() { return getenv("MI355_NO_EQRM") != nullptr; }
+// MI355_EQRM_COMPACT=0 (A/B timing): pdsch_eq_rm's lean path gathers through the inverse table, no compact image
+inline bool env_eqrm_compact() { static const bool v = !getenv("MI355_EQRM_COMPACT") || env_int("MI355_EQRM_COMPACT") != 0; return v; }
+// MI355_EQRM_DIAG (measurement only, wrong results): 1 = pdsch_eq_rm without rate dematching, 2 = without equalisation
+inline int env_eqrm_diag() { static const int v = env_int("MI355_EQRM_DIAG"); return v; }
 
 using HostTime =std::chrono::steady_clock::time_point;
 inline HostTime host_now() { return std::chrono::steady_clock::now(); }

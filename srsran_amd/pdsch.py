@@ -64,6 +64,8 @@ def _declare():
     L.mi355_pdsch_create.argtypes = [C.POINTER(vp), C.POINTER(Cell), u32, i32]
     L.mi355_pdsch_destroy.argtypes = [vp]
     L.mi355_pdsch_decode_batch.argtypes = [vp, vp, C.POINTER(PdschJob), u32, C.POINTER(PdschRes), vp]
+    L.mi355_pdsch_decode_launch.argtypes = [vp, vp, C.POINTER(PdschJob), u32, C.POINTER(PdschRes), vp]
+    L.mi355_pdsch_decode_collect.argtypes = [vp]
     L.mi355_pdsch_frontend.argtypes = [vp, C.POINTER(PdschJob), u32, vp]
     L.mi355_pdsch_debug_stage.argtypes = [vp, u32, u32, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.mi355_pdsch_set_llr_8bit.argtypes = [vp, C.c_int]
@@ -142,6 +144,19 @@ class Pdsch:
                 out[i] = res[i]
         check(self.L.mi355_pdsch_decode_batch(self.h, pool.h, arr, n, out, None), "pdsch_decode_batch")
         return out
+
+    def decode_launch(self, pool: SoftbufferPool, jobs: list[PdschJob]) -> tuple:
+        """mi355_pdsch_decode_launch: (return code, the (njobs, 2) PdschRes array filled by decode_collect).  The
+        receiver keeps the arrays alive until then."""
+        n = len(jobs)
+        arr, out = (PdschJob * n)(*jobs), (PdschRes * (2 * n))()
+        self._in_flight = getattr(self, "_in_flight", []) + [(arr, out)]
+        return self.L.mi355_pdsch_decode_launch(self.h, pool.h, arr, n, out, None), out
+
+    def decode_collect(self) -> int:
+        r = self.L.mi355_pdsch_decode_collect(self.h)
+        self._in_flight = []
+        return r
 
     def frontend(self, jobs: list[PdschJob]):
         n = len(jobs)

@@ -139,7 +139,7 @@ def features(K: int, rv: int, E: int, e_offset: int, Qm: int = 2, fresh: bool = 
             "empty_rows": (P0, P1),                           # rm_image.h rm_rowmask_word (fresh 16-window buffers)
             "sparse": n == 16 and 0 < P0 + P1,                # dlsch_kernels.hip:142: rows left unwritten
             "rows_mixed": n == 16 and 0 < P0 + P1 < 2 * (K // 16),
-            # pdsch_runtime.cpp plan_eq_rm: pdsch_eq_rm (and its compact tables, dlsch_tables.h) only without wrap
+            # pdsch_plan.h eqrm_job_shape: pdsch_eq_rm (and its compact tables, dlsch_tables.h) only without wrap
             "eqrm_ok": E + Qm <= N}
 
 
