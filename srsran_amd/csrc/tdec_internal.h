@@ -44,6 +44,9 @@ struct TdecWinArgs {
   // the buffers are softbuffer-pool slots (in_stride == SB_STRIDE) carrying the parity-row bitmaps of the rate
   // dematcher at SB_ROWMASK (dlsch_internal.h): parity rows without an LLR are not read
   int             rowmask;
+  // 16 zero bytes, 16-byte aligned, read-only (mi355_tdec_batch::zero16): what the 16-byte-load path reads in place
+  // of a parity row without an LLR; nullptr keeps every wave on the 4-byte path
+  const uint4*    zero16;
 };
 
 struct TdecDecideArgs {

@@ -248,12 +248,21 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
       return true;
     }
   };
-  // 8 steps j0..j0+7 of a softbuffer stream as two 16-byte pieces (the parity stream's pieces of empty rows: zero)
+  // 8 steps j0..j0+7 of a softbuffer stream as two 16-byte pieces.  The parity stream's pieces of empty rows are
+  // zero: the lane selects the address, not the value, and reads the launch's 16-byte zero block (a.zero16) instead,
+  // so every lane issues both loads and the compiler's count of loads in flight stays exact (a predicated load is a
+  // branch around it, and at the join behind it the wait-count pass assumes the fewer loads pending)
   auto tx_load = [&](int so, int j0, uint32_t* r, bool par = false) {
-    uint4 v0 = make_uint4(0u, 0u, 0u, 0u), v1 = v0;
-    const int tc = (q >> 1) & 7, jr = j0 + (q >> 4);
-    if (!par || yrow(tc, jr)) v0 = txin[so + j0 * 2];
-    if (!par || yrow(tc, jr + 4)) v1 = txin[so + (j0 + 4) * 2];
+    const int    tc = (q >> 1) & 7, jr = j0 + (q >> 4);
+    const uint4* p0 = txin + so + j0 * 2;
+    const uint4* p1 = txin + so + (j0 + 4) * 2;
+    if constexpr (RMK) {
+      if (par) {
+        p0 = yrow(tc, jr) ? p0 : a.zero16;
+        p1 = yrow(tc, jr + 4) ? p1 : a.zero16;
+      }
+    }
+    const uint4 v0 = *p0, v1 = *p1;
     r[0] = v0.x; r[1] = v0.y; r[2] = v0.z; r[3] = v0.w;
     r[4] = v1.x; r[5] = v1.y; r[6] = v1.z; r[7] = v1.w;
   };
@@ -304,6 +313,31 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
   }
 
   if constexpr (DIAG != 2) {
+  // ------------------------------------------------ backward pass: its first two segments, in flight over the warm-up
+  uint32_t cx[SEG], cy[SEG], ca[SEG] = {};
+  auto     load = [&](int t, uint32_t* x, uint32_t* y, uint32_t* ap) {
+    if constexpr (TX) { // raw 16-byte pieces, transposed when the segment is consumed
+      if constexpr (!dec2) tx_load(txoX, t * SEG, x);
+      tx_load(txoY, t * SEG, y, true);
+    }
+#pragma unroll
+    for (int i = 0; i < SEG; i++) {
+      const int j = FULL ? t * SEG + i : min(t * SEG + i, L - 1); // clamp the ragged last segment
+      if constexpr (!TX || dec2) x[i] = X[j * xs];
+      if constexpr (!TX) y[i] = yrow(cbg, j) ? Y[j * ys] : 0u;
+      if constexpr (has_ap) ap[i] = AP[j * 64];
+    }
+  };
+  // two segments in flight ahead of the one being consumed (registers are free in this pass).  The three
+  // register sets rotate by position in a loop unrolled three times, so no copies move them between segments.
+  // Every load here is unconditional: a prefetch behind an `if` is a join of a path with loads and one without,
+  // where the compiler's wait-count pass assumes the fewer pending and waits for the segments meant to stay in
+  // flight.  So the loop runs whole triples, each segment prefetching segment max(t - 2, 0) (past the first segment
+  // it reads segment 0 once more: rows the pass reads anyway), and the one or two segments left after the last
+  // triple run without a prefetch.
+  uint32_t bx[SEG], by[SEG], ba[SEG] = {}, dx[SEG], dy[SEG], da[SEG] = {};
+  load(nseg - 1, cx, cy, ca);
+  load(max(nseg - 2, 0), bx, by, ba);
   // ------------------------------------------------ backward pass: boundary (row L)
   // warm-up over the first 40 steps of the NEXT window (lane q+1 holds windows 2l+2, 2l+3), from -INF
   // (turbodecoder_win.h:566-631).  The neighbour value of lane NL-1 belongs to another code block and
@@ -356,28 +390,12 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
 
   // ------------------------------------------------ backward pass: main, one checkpoint per segment
   {
-    uint32_t cx[SEG], cy[SEG], ca[SEG] = {};
-    auto     load = [&](int t, uint32_t* x, uint32_t* y, uint32_t* ap) {
-      if constexpr (TX) { // raw 16-byte pieces, transposed when the segment is consumed
-        if constexpr (!dec2) tx_load(txoX, t * SEG, x);
-        tx_load(txoY, t * SEG, y, true);
-      }
-#pragma unroll
-      for (int i = 0; i < SEG; i++) {
-        const int j = FULL ? t * SEG + i : min(t * SEG + i, L - 1); // clamp the ragged last segment
-        if constexpr (!TX || dec2) x[i] = X[j * xs];
-        if constexpr (!TX) y[i] = yrow(cbg, j) ? Y[j * ys] : 0u;
-        if constexpr (has_ap) ap[i] = AP[j * 64];
-      }
-    };
-    // two segments in flight ahead of the one being consumed (registers are free in this pass).  The three
-    // register sets rotate by position in a loop unrolled three times, so no copies move them between segments.
-    uint32_t bx[SEG], by[SEG], ba[SEG] = {}, dx[SEG], dy[SEG], da[SEG] = {};
-    load(nseg - 1, cx, cy, ca);
-    if (nseg > 1) load(nseg - 2, bx, by, ba);
-    auto seg = [&](int t, const uint32_t* rx, const uint32_t* ry, const uint32_t* sa, uint32_t* lx, uint32_t* ly,
-                   uint32_t* la) {
+    auto seg = [&](int t, bool pf, const uint32_t* rx, const uint32_t* ry, const uint32_t* sa, uint32_t* lx,
+                   uint32_t* ly, uint32_t* la) {
       uint32_t sx[SEG], sy[SEG];
+      // (the scheduler otherwise hoists this segment's transposition writes, and with them the wait for its loads,
+      // into the segment before, whose prefetch that wait then drains)
+      __builtin_amdgcn_sched_barrier(0);
       if constexpr (TX) {
         if constexpr (!dec2) tx_unpack(0, rx, sx);
         tx_unpack(1, ry, sy);
@@ -387,7 +405,7 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
         if constexpr (!TX || dec2) sx[i] = rx[i];
         if constexpr (!TX) sy[i] = ry[i];
       }
-      if (t > 1) load(t - 2, lx, ly, la);
+      if (pf) load(max(t - 2, 0), lx, ly, la);
 #pragma unroll
       for (int i = SEG - 1; i >= 0; i--) {
         const int k = t * SEG + i;
@@ -415,12 +433,16 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
         }
       }
     };
+    int t = nseg - 1;
 #pragma unroll 1
-    for (int t = nseg - 1; t >= 0; t -= 3) {
-      seg(t, cx, cy, ca, dx, dy, da);
-      if (t >= 1) seg(t - 1, bx, by, ba, cx, cy, ca);
-      if (t >= 2) seg(t - 2, dx, dy, da, bx, by, ba);
+    for (; t >= 2; t -= 3) {
+      seg(t, true, cx, cy, ca, dx, dy, da);
+      seg(t - 1, true, bx, by, ba, cx, cy, ca);
+      seg(t - 2, true, dx, dy, da, bx, by, ba);
     }
+    // nseg % 3 segments are left (t = nseg % 3 - 1), loaded by the last triple or, for nseg < 3, above
+    if (t >= 0) seg(t, false, cx, cy, ca, dx, dy, da);
+    if (t >= 1) seg(t - 1, false, bx, by, ba, cx, cy, ca);
   }
   } // DIAG != 2
   if constexpr (DIAG == 1 || DIAG == 3 || DIAG == 4) {
@@ -536,6 +558,7 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
   auto fseg = [&](int t, const uint32_t* rx, const uint32_t* ry, const uint32_t* ca, const uint32_t* cd,
                   const uint32_t* cc, uint32_t* nx, uint32_t* ny, uint32_t* na, uint32_t* nd, uint32_t* nc) {
     uint32_t cx[SEG], cy[SEG];
+    __builtin_amdgcn_sched_barrier(0); // (as in the backward pass: this segment's waits stay behind the last one's compute)
     if constexpr (TX) {
       if constexpr (!dec2) tx_unpack(0, rx, cx);
       tx_unpack(1, ry, cy);
@@ -548,7 +571,9 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
     const int s0 = t * SEG;
     const int e  = FULL ? s0 + SEG : ((s0 + SEG < L) ? s0 + SEG : L);
     uint32_t  bits = 0; // decision bits of the segment: window 2l in bits 8..15, 2l+1 in 0..7 (MSB first)
-    if (t + 1 < nseg) load(t + 1, nx, ny, na, nd, nc);
+    // unconditional (the last segment prefetches itself once more, rows and checkpoints this segment has read): behind
+    // an `if` the join would make the compiler wait for most of these loads before the segment's compute
+    load(min(t + 1, nseg - 1), nx, ny, na, nd, nc);
 
     v2s xin[SEG];
 #pragma unroll
@@ -669,6 +694,11 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
       bb[L / 8]   = (uint8_t)bits;
     }
   };
+  // Segment 0's loads land before the loop (s_waitcnt vmcnt(0), once per half-iteration).  The loop header joins this
+  // path with the back edge, and for each register the wait-count pass keeps the later of its two queue positions:
+  // the loads above are scheduled in another order than the loop's own prefetch, so left pending they would turn the
+  // first wait of every other segment into vmcnt(0) and drain the prefetch issued a segment before.
+  __builtin_amdgcn_s_waitcnt(0x0f70);
 #pragma unroll 1
   for (int t = 0; t < nseg; t += 2) {
     fseg(t, cx, cy, ca, cd, cc, nx, ny, na, nd, nc);
@@ -830,9 +860,9 @@ template <int NSB, int DIAG, bool FULL, int OUTK>
 static void launch_mode_o(int mode, int blocks, const TdecWinArgs& a, hipStream_t s)
 {
   // 16-byte pieces need every code block's buffer (and so the stream offsets, multiples of 16 bytes for these K)
-  // 16-byte aligned
+  // 16-byte aligned, and the zero block the empty parity rows are read from
   if constexpr (NSB == 16 && FULL && (DIAG == 0 || DIAG == 20)) {
-    if (tx_enabled() && (uintptr_t)a.in % 16 == 0 && (a.in_stride * sizeof(int16_t)) % 16 == 0 && (a.L * 16 + 32) % 16 == 0) {
+    if (tx_enabled() && a.zero16 && (uintptr_t)a.in % 16 == 0 && (a.in_stride * sizeof(int16_t)) % 16 == 0 && (a.L * 16 + 32) % 16 == 0) {
       launch_mode_t<NSB, DIAG, FULL, OUTK, true>(mode, blocks, a, s);
       return;
     }

@@ -73,6 +73,7 @@ struct mi355_tdec_batch {
   int                          gen_cb   = -1; // generic decoder: per-code-block workgroups (1), pair lanes (0), auto (-1)
   int                          gen_warm = 32; // its guessed-state warm-up (rows / steps)
   DevMem                       reruns;            // device counter (uint32_t) of its chunk reruns
+  DevMem                       zero16;            // TdecWinArgs::zero16, zeroed once at creation
   bool                         prof = false;
   std::vector<hipEvent_t>      ev;
   size_t                       ev_used = 0;
@@ -162,7 +163,10 @@ int mi355_tdec_batch_create(mi355_tdec_batch_t** q, int device)
   CHECK_HIP(hipSetDevice(device));
   auto* b   = new mi355_tdec_batch;
   b->device = device;
-  if (hipStreamCreateWithFlags(&b->own, hipStreamNonBlocking) != hipSuccess) {
+  // (upload waits for the copy: the kernels that read the block run on non-blocking streams)
+  const std::vector<uint32_t> zero(64, 0u);
+  if (hipStreamCreateWithFlags(&b->own, hipStreamNonBlocking) != hipSuccess || b->zero16.upload(zero) != hipSuccess) {
+    if (b->own) (void)hipStreamDestroy(b->own);
     delete b;
     return MI355_ERROR;
   }
@@ -282,6 +286,7 @@ int mi355_tdec_run_internal(mi355_tdec_batch_t* q, const TdecRun& rq)
         TdecWinArgs wa{d_in, in_stride, rq.in_idx, rq.done, rq.remaining, A1, E, D, CK, dstE, dstA,
                        (int)n, (int)g.L, (int)g.Lp, (int)g.nseg, (int)h, 0, nullptr, out_stride};
         wa.rowmask = rq.rowmask && g.nsb == 16 && in_stride == SB_STRIDE;
+        wa.zero16  = q->zero16.as<uint4>();
         CHECK_HIP(tdec_win_launch_halfit(g.nsb, wa, s));
         continue;
       }
@@ -289,6 +294,7 @@ int mi355_tdec_run_internal(mi355_tdec_batch_t* q, const TdecRun& rq)
                      (int)n, (int)g.L, (int)g.Lp, (int)g.nseg, (int)h, h + 1 == h1,
                      (fuse && h + 1 == h1) ? d_out : nullptr, out_stride};
       wa.rowmask = rq.rowmask && g.nsb == 16 && in_stride == SB_STRIDE;
+      wa.zero16  = q->zero16.as<uint4>();
       if (rq.spec && fuse && h + 1 == h1 && tdec_win_spec_ok(g.nsb, g.L)) {
         wa.spec = 1;
         if (rq.spec_taken) *rq.spec_taken = true;
