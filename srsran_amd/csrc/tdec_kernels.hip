@@ -51,11 +51,13 @@ __device__ __forceinline__ uint32_t from_next(uint32_t v)
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x101, 0xf, 0xf, true);
 }
 
-// natural decision bit m (MSB first within its byte, turbodecoder_win.h:973-993) into an LDS byte bitmap
+// natural decision bit m (MSB first within its byte, turbodecoder_win.h:973-993) into an LDS byte bitmap.  Every lane
+// issues the OR, with a zero operand where the bit is clear: behind `if (v)` each call is an exec-masked region of its
+// own, 16 a segment, and the segment's trellis arithmetic and LDS traffic cannot be scheduled across them.
 __device__ __forceinline__ void bm_set(uint32_t* bm, uint32_t m, bool v)
 {
-  const uint32_t by = m >> 3;
-  if (v) atomicOr(&bm[by >> 2], 1u << (((by & 3) << 3) + 7 - (m & 7)));
+  // byte m >> 3 is byte (m >> 3) & 3 of word m >> 5 and the bit is 7 - (m & 7) of it: bit (m & 31) ^ 7 of the word
+  __hip_atomic_fetch_or(&bm[m >> 5], (uint32_t)v << ((m & 31u) ^ 7u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
 // ---------------------------------------------------------------------------- fused code-block check
@@ -263,14 +265,31 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
       }
     }
     const uint4 v0 = *p0, v1 = *p1;
-    r[0] = v0.x; r[1] = v0.y; r[2] = v0.z; r[3] = v0.w;
-    r[4] = v1.x; r[5] = v1.y; r[6] = v1.z; r[7] = v1.w;
+    if constexpr (dec2) {
+      // whole pieces, so that a piece crosses the forward loop's back edge as one 16-byte value.  Carried as four
+      // words, two of them are copied out of the load's registers at the top of the block that ends the loop; DEC2's
+      // segment is one block (bm_set has no branch), so that copy would wait for a piece right after its load was
+      // issued, at the start of the segment's compute (DEC1's code stays as it was compiled)
+      __builtin_memcpy(r, &v0, 16);
+      __builtin_memcpy(r + 4, &v1, 16);
+    } else {
+      r[0] = v0.x; r[1] = v0.y; r[2] = v0.z; r[3] = v0.w;
+      r[4] = v1.x; r[5] = v1.y; r[6] = v1.z; r[7] = v1.w;
+    }
   };
   // the lane's own words of those 8 steps (buffer b of the wave)
   auto tx_unpack = [&](int b, const uint32_t* r, uint32_t* o) {
     uint32_t* w = txb + b * SEG * 64;
-    ((uint4*)w)[q]      = make_uint4(r[0], r[1], r[2], r[3]);
-    ((uint4*)w)[64 + q] = make_uint4(r[4], r[5], r[6], r[7]);
+    if constexpr (dec2) { // (whole pieces, as tx_load left them)
+      uint4 p0, p1;
+      __builtin_memcpy(&p0, r, 16);
+      __builtin_memcpy(&p1, r + 4, 16);
+      ((uint4*)w)[q]      = p0;
+      ((uint4*)w)[64 + q] = p1;
+    } else {
+      ((uint4*)w)[q]      = make_uint4(r[0], r[1], r[2], r[3]);
+      ((uint4*)w)[64 + q] = make_uint4(r[4], r[5], r[6], r[7]);
+    }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -607,8 +626,8 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
             if constexpr (wr_a1) put(i, tb, out);
             if constexpr (wr_bm) {
               const uint32_t jd = (tb & 0xffffu) >> 7, wlo = tb & 15u, whi = (tb >> 16) & 15u;
-              bm_set(bm, wlo * L + jd, out.x > 0);
-              bm_set(bm, whi * L + jd, out.y > 0);
+              bm_set(bm, __umul24(wlo, (uint32_t)L) + jd, out.x > 0); // (a 24-bit multiply-add, not a 64-bit one)
+              bm_set(bm, __umul24(whi, (uint32_t)L) + jd, out.y > 0);
             }
           }
         }
@@ -676,8 +695,8 @@ __device__ __forceinline__ void tdec_win_body(const TdecWinArgs& a, const int gl
             if constexpr (wr_a1) put(i, tb, out - xin[i]);
             if constexpr (wr_bm) { // natural bit w*L + j' (turbodecoder_win.h:973-993)
               const uint32_t jd = (tb & 0xffffu) >> 7, wlo = tb & 15u, whi = (tb >> 16) & 15u;
-              bm_set(bm, wlo * L + jd, out.x > 0);
-              bm_set(bm, whi * L + jd, out.y > 0);
+              bm_set(bm, __umul24(wlo, (uint32_t)L) + jd, out.x > 0); // (a 24-bit multiply-add, not a 64-bit one)
+              bm_set(bm, __umul24(whi, (uint32_t)L) + jd, out.y > 0);
             }
             if constexpr (wr_d) {
               D16[olo] = out.x;
