@@ -4,6 +4,7 @@
 #include <stdio.h>
 
 #include "lte_common.h"
+#include "sync_internal.h"
 #include "ue_dl_object.h"
 
 using namespace mi355;
@@ -53,18 +54,9 @@ int mi355_ue_dl_create(mi355_ue_dl_t** q, const mi355_cell_t* cell, uint32_t nof
   d->cell   = *cell;
   d->nof_rx = nof_rx_antennas;
   const std::vector<float2> pil = crs_table(*cell);
-  // srslte_pss_generate (sync/pss.c:346-375) for N_id_2 = cell.id % 3, the same float / double expression
+  // srslte_pss_generate (sync/pss.c:346-375) for N_id_2 = cell.id % 3
   std::vector<float2> pss(62);
-  {
-    const float root_value[] = {25.0, 29.0, 34.0};
-    const int   sign         = -1;
-    const float root         = root_value[cell->id % 3];
-    for (int i = 0; i < 62; i++) {
-      const float arg = i < 31 ? (float)sign * M_PI * root * ((float)i * ((float)i + 1.0)) / 63.0
-                               : (float)sign * M_PI * root * (((float)i + 2.0) * ((float)i + 1.0)) / 63.0;
-      pss[i] = make_float2(cosf(arg), sinf(arg));
-    }
-  }
+  pss_sequence(cell->id % 3, pss.data());
   if (hipStreamCreateWithFlags(&d->own, hipStreamNonBlocking) != hipSuccess || set_dft(d) != MI355_SUCCESS ||
       d->pilots.upload(pil) != hipSuccess || d->pss.upload(pss) != hipSuccess ||
       mi355_pdsch_create(&d->pdsch, cell, nof_rx_antennas, device) != MI355_SUCCESS) {

@@ -46,6 +46,23 @@ def put_refs(cell: Cell, tti: int, grids: np.ndarray) -> None:
     check(L.mi355_refsignal_cs_put_sf_host(C.byref(cell), tti, g), "refsignal_cs_put_sf_host")
 
 
+def put_sync(cell: Cell, sf_idx: int, grids: np.ndarray) -> None:
+    """Opt-in: PSS and SSS of the cell into a host subframe grid (srslte_pss_put_slot / srslte_sss_put_slot into slot 0,
+    FDD), for subframes 0 and 5; other subframes are left alone.  grids: (nof_ports, 2 * nsymb * 12 * nof_prb)
+    complex64; as in srslte_enb_dl_put_sync the signals go onto every port.  Nothing calls this by default: a
+    generator that does not ask for it writes the grids it always wrote."""
+    from . import sync as S
+    if sf_idx not in (0, 5):
+        return
+    assert grids.dtype == np.complex64 and grids.flags.c_contiguous
+    nsymb = 7 if cell.cp == S.CP_NORM else 6
+    pss, sss = S.pss_generate(cell.id % 3), S.sss_generate(cell.id)[0 if sf_idx == 0 else 1]
+    for p in range(grids.shape[0]):
+        slot0 = grids[p][: nsymb * 12 * cell.nof_prb]
+        S.pss_put_slot(pss, slot0, cell.nof_prb, cell.cp)
+        S.sss_put_slot(sss, slot0, cell.nof_prb, cell.cp)
+
+
 class EnbPdschJob(C.Structure):
     """mi355_enb_dl_pdsch_job_t: one srslte_enb_dl_put_pdsch call (device payloads and port grids)."""
     _fields_ = [("sf", DlSfCfg), ("cfg", PdschCfg), ("data", C.c_void_p * 2), ("sf_symbols", C.c_void_p * 4)]
