@@ -1,5 +1,6 @@
-// srsran_amd/csrc/lte_common.h -- host-side LTE helpers shared by the runtimes: the 36.211 7.2 Gold
-// sequence and the cell-specific reference signal table / positions (refsignal_dl.c:63-114, :214-290).
+// srsran_amd/csrc/lte_common.h -- LTE helpers shared by the runtimes: the 36.211 7.2 Gold sequence and the
+// cell-specific reference signal table (host) and the CRS positions (host and device: LTE_HD), refsignal_dl.c:63-114,
+// :214-290.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +9,12 @@
 #include <vector>
 
 #include "../../include/srsran_amd/pdsch.h"
+
+#ifdef __HIPCC__
+#define LTE_HD __host__ __device__
+#else
+#define LTE_HD
+#endif
 
 namespace mi355 {
 
@@ -49,13 +56,13 @@ inline std::vector<uint32_t> gold_table(uint32_t len)
   return t;
 }
 
-inline uint32_t crs_nsymbol(uint32_t l, uint32_t nsymb, uint32_t port)
+LTE_HD inline uint32_t crs_nsymbol(uint32_t l, uint32_t nsymb, uint32_t port)
 {
   if (port < 2) return (l % 2) ? (l / 2 + 1) * nsymb - 3 : (l / 2) * nsymb;
   return 1 + l * nsymb;
 }
 
-inline uint32_t crs_v(uint32_t port, uint32_t l)
+LTE_HD inline uint32_t crs_v(uint32_t port, uint32_t l)
 {
   switch (port) {
     case 0: return (l % 2) ? 3 : 0;
@@ -65,7 +72,7 @@ inline uint32_t crs_v(uint32_t port, uint32_t l)
   }
 }
 
-inline uint32_t crs_fidx(uint32_t id, uint32_t l, uint32_t port) { return (crs_v(port, l) + id % 6) % 6; }
+LTE_HD inline uint32_t crs_fidx(uint32_t id, uint32_t l, uint32_t port) { return (crs_v(port, l) + id % 6) % 6; }
 
 // srslte_refsignal_cs_set_cell: pilots[pair][sf][4 * 2 * nof_prb] (pair 0: ports 0/1 over 4 symbols,
 // pair 1: ports 2/3 over 2 symbols)
